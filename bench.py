@@ -1,8 +1,13 @@
 """Headline benchmark: real-time factor of Zonos-v0.1-transformer generate() + DAC decode on MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the headline JSON line. `--full` adds everything else
+the bench measures to that line: the decode step and its per-kernel / roofline tables, the utterance breakdown, the
+`widened` configurations, the C3 sharded batch, the end-of-batch gather and the CPU baseline. `--dump-outputs DIR`
+writes what the last timed step returned (codes and waveform) as DIR/<name>.npy.
 
 Workload (BASELINE.json configs[1]): one utterance per GPU per step —
 batch=1, Lc=160 synthetic prefix-conditioning rows, 861 new frames (10 s of 44.1 kHz audio),
@@ -749,11 +754,93 @@ def dry_run(args, rank: int, world: int) -> None:
         dist.destroy_process_group()
 
 
+def dump_outputs(path: str, rank: int, codes, wav) -> None:
+    """--dump-outputs: what the last timed step returned to its caller, as float32 arrays: codes.npy [1, 9, frames]
+    (integers below 1025, exact in float32) and wav.npy [1, 1, samples]. Ranks above 0 add `_rank<r>` to the name."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    tag = f"_rank{rank}" if rank else ""
+    np.save(os.path.join(path, f"codes{tag}.npy"), codes.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(path, f"wav{tag}.npy"), wav.float().cpu().numpy())
+
+
+def full_measurements(args, model, cfg, cond, codes, ref_codes, dev, cdev, rank: int, world: int, dist) -> dict:
+    """--full: everything the bench measures besides the headline figure, as further keys of the result line (all of
+    it after the timed steps, on the same model)."""
+    n_new = args.new_tokens
+    # optional end-of-batch gather of every rank's codes to rank 0 (SURVEY.md §8e; outside the timed
+    # region): int16 payload over RCCL/xGMI
+    gather = None
+    if dist:
+        from zonos_vibes_amd.shard import gather_codes
+        g0 = time.perf_counter()  # fatal on failure (see time_c3_sharded)
+        got = gather_codes([codes], [rank], world, device=cdev)
+        torch.cuda.synchronize()
+        gather = {"ok": True, "ms": round((time.perf_counter() - g0) * 1e3, 2)}
+        if rank == 0:
+            gather["frames_gathered"] = int(sum(c.shape[-1] for c in got))
+
+    # kernel-level measurement (outside the timed region)
+    step_us, step_pos = time_decode_step(model, cond)
+    ktab = kernel_table(model, cond)
+    roof, roof_next = dominant_kernels(ktab)
+    widened = time_widened_rows(model, dev)
+    if rank == 0 and not args.no_default_cap:
+        widened["default_capacity"] = time_default_capacity(dev, n_new, ref_codes)
+        widened["batch1_30s"] = time_long_utterance(dev)
+    if rank == 0 and not args.no_hybrid:
+        widened["hybrid_c4"] = time_hybrid(dev, n_new)
+    if rank == 0 and not args.no_c5:
+        widened["c5_share"] = time_c5(dev)
+    breakdown = utterance_breakdown(model, cond, n_new)
+    dac_tf = DAC_FLOP_PER_FRAME * n_new / (breakdown["dac_decode_ms"] * 1e-3) / 1e12
+    c3 = None
+    if not args.no_batch:
+        c3 = time_c3_sharded(model, dev, rank, world, dist, per_gpu=args.c3_per_gpu, cdev=cdev)  # last: grows the engine
+    if rank != 0:
+        return {}
+    out = {
+        "decode_step_us": round(step_us, 1), "decode_step_pos": step_pos,
+        "decode_step_hbm_frac": round(step_bytes(model, step_pos) / (step_us * 1e-6) / 1e9 / HBM_PEAK_GBS, 3),
+        "roofline": roof,
+        "roofline_next": roof_next,
+        "c2_step_kernels": ktab,
+        "utterance_breakdown": breakdown,
+        "dac_decode_roofline": {"bound": "mfma", "achieved": round(dac_tf, 1), "peak": MFMA_PEAK_TFLOPS,
+                                "unit": "TFLOP/s", "frac": round(dac_tf / MFMA_PEAK_TFLOPS, 4),
+                                "flop_per_frame": DAC_FLOP_PER_FRAME, "frames": n_new,
+                                "ms": breakdown["dac_decode_ms"],
+                                "mfma_busy_source": "profiles/r06_dac_mfma_pmc.json (SQ_VALU_MFMA_BUSY_CYCLES pass)"},
+        "c3_sharded": c3,
+        "widened": widened,
+        "end_of_batch_gather": gather,
+    }
+    if world == 1 and not args.no_cpu_baseline:
+        sd = {}
+        for sp in syn.zonos_specs(cfg):
+            t = torch.empty(sp.shape, dtype=torch.bfloat16, device=dev)
+            _lib.check(_lib.lib().zmi_fill_uniform(t.data_ptr(), sp.numel, syn.tensor_key(0, sp.name), sp.scale,
+                                                   sp.offset, 0, torch.cuda.current_stream().cuda_stream))
+            sd[sp.name] = t
+        sd["heads.0.weight"][1024] = 0
+        torch.cuda.synchronize()
+        out["cpu_baseline"] = cpu_baseline(sd, cfg)
+    else:
+        out["cpu_baseline"] = None
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (codes, wav) as DIR/<name>.npy, float32")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline run, also measure the decode step, its kernel / roofline tables, the "
+                         "utterance breakdown, the `widened` configurations, the C3 sharded batch, the end-of-batch "
+                         "gather and the CPU baseline (the --no-* options below trim this part)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--new-tokens", type=int, default=N_NEW)
     ap.add_argument("--no-hybrid", action="store_true", help="skip the C4 hybrid-backbone line in `widened`")
@@ -809,10 +896,13 @@ def main():
         wav = model.autoencoder.decode(codes)
         return codes, wav
 
-    for _ in range(max(1, args.warmup)):
+    if args.steps < 1:
+        raise SystemExit("bench: --steps must be at least 1")
+    ref_codes = None
+    for _ in range(args.warmup):
         codes, wav = one_utterance()
+        ref_codes = codes.clone()
     torch.cuda.synchronize()
-    ref_codes = codes.clone()
     if dist:
         dist.barrier()
     torch.cuda.synchronize()
@@ -829,7 +919,10 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     assert codes.shape[-1] == n_new and wav.shape[-1] == n_new * DAC_HOP, (codes.shape, wav.shape)
-    # every timed utterance decoded exactly the warm-up's codes (greedy: a silent change fails the run)
+    # every timed utterance decoded exactly the warm-up's codes, or the first timed one's when there was no warm-up
+    # (greedy: a silent change fails the run)
+    if ref_codes is None:
+        ref_codes = timed_codes[0].clone()
     for c in timed_codes:
         if not torch.equal(c, ref_codes):
             raise SystemExit("bench: a timed utterance's codes differ from the warm-up's (non-deterministic decode)")
@@ -845,79 +938,28 @@ def main():
     audio_s = frames * DAC_HOP / DAC_SAMPLE_RATE
     rtf = audio_s / elapsed
 
-    # optional end-of-batch gather of every rank's codes to rank 0 (outside the timed
-    # region): int16 payload over RCCL/xGMI
-    gather = None
-    if dist:
-        from zonos_vibes_amd.shard import gather_codes
-        g0 = time.perf_counter()  # fatal on failure (see time_c3_sharded)
-        got = gather_codes([codes], [rank], world, device=cdev)
-        torch.cuda.synchronize()
-        gather = {"ok": True, "ms": round((time.perf_counter() - g0) * 1e3, 2)}
-        if rank == 0:
-            gather["frames_gathered"] = int(sum(c.shape[-1] for c in got))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, codes, wav)
 
-    # kernel-level measurement (outside the timed region)
-    step_us, step_pos = time_decode_step(model, cond)
-    ktab = kernel_table(model, cond)
-    roof, roof_next = dominant_kernels(ktab)
-    widened = time_widened_rows(model, dev)
-    if rank == 0 and not args.no_default_cap:
-        widened["default_capacity"] = time_default_capacity(dev, n_new, ref_codes)
-        widened["batch1_30s"] = time_long_utterance(dev)
-    if rank == 0 and not args.no_hybrid:
-        widened["hybrid_c4"] = time_hybrid(dev, n_new)
-    if rank == 0 and not args.no_c5:
-        widened["c5_share"] = time_c5(dev)
-    breakdown = utterance_breakdown(model, cond, n_new)
-    dac_tf = DAC_FLOP_PER_FRAME * n_new / (breakdown["dac_decode_ms"] * 1e-3) / 1e12
-    c3 = None
-    if not args.no_batch:
-        c3 = time_c3_sharded(model, dev, rank, world, dist, per_gpu=args.c3_per_gpu, cdev=cdev)  # last: grows the engine
-    out = None
+    out = {
+        "metric": "real-time factor (44kHz audio s/compute s) + DAC tokens/s/GPU, Zonos-transformer",
+        "value": round(rtf, 3), "unit": "x realtime (audio s / wall s, all GPUs)",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 2),
+        "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": round(rtf / BASELINE_RTF, 3),
+        "dtype": "bf16", "data": "synthetic",
+        "config": {"workload": f"C2: batch=1 per GPU, Lc={LC}, {n_new} frames ({n_new * DAC_HOP / DAC_SAMPLE_RATE:.2f}"
+                               f" s audio), greedy + rep. penalty, EOS suppressed, + DAC decode",
+                   "global_batch": world, "seq_len": LC + n_new + 9, "parallelism": f"dp{world} (utterance-sharded)",
+                   "decode_steps": n_new + 8},
+        "dac_tokens_per_s_per_gpu": round(frames * 9 / elapsed / world, 1),
+        "frames_per_s_per_gpu": round(frames / elapsed / world, 1),
+        "codes_sha256_16": codes_sha,
+    }
+    if args.full:
+        out.update(full_measurements(args, model, cfg, cond, codes, ref_codes, dev, cdev, rank, world, dist))
     if rank == 0:
-        out = {
-            "metric": "real-time factor (44kHz audio s/compute s) + DAC tokens/s/GPU, Zonos-transformer",
-            "value": round(rtf, 3), "unit": "x realtime (audio s / wall s, all GPUs)",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 2),
-            "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": round(rtf / BASELINE_RTF, 3),
-            "dtype": "bf16", "data": "synthetic",
-            "config": {"workload": f"C2: batch=1 per GPU, Lc={LC}, {n_new} frames ({n_new * DAC_HOP / DAC_SAMPLE_RATE:.2f}"
-                                   f" s audio), greedy + rep. penalty, EOS suppressed, + DAC decode",
-                       "global_batch": world, "seq_len": LC + n_new + 9, "parallelism": f"dp{world} (utterance-sharded)",
-                       "decode_steps": n_new + 8},
-            "dac_tokens_per_s_per_gpu": round(frames * 9 / elapsed / world, 1),
-            "frames_per_s_per_gpu": round(frames / elapsed / world, 1),
-            "decode_step_us": round(step_us, 1), "decode_step_pos": step_pos,
-            "decode_step_hbm_frac": round(step_bytes(model, step_pos) / (step_us * 1e-6) / 1e9 / HBM_PEAK_GBS, 3),
-            "roofline": roof,
-            "roofline_next": roof_next,
-            "codes_sha256_16": codes_sha,
-            "c2_step_kernels": ktab,
-            "utterance_breakdown": breakdown,
-            "dac_decode_roofline": {"bound": "mfma", "achieved": round(dac_tf, 1), "peak": MFMA_PEAK_TFLOPS,
-                                    "unit": "TFLOP/s", "frac": round(dac_tf / MFMA_PEAK_TFLOPS, 4),
-                                    "flop_per_frame": DAC_FLOP_PER_FRAME, "frames": n_new,
-                                    "ms": breakdown["dac_decode_ms"],
-                                    "mfma_busy_source": "profiles/r06_dac_mfma_pmc.json (SQ_VALU_MFMA_BUSY_CYCLES pass)"},
-            "c3_sharded": c3,
-            "widened": widened,
-            "end_of_batch_gather": gather,
-        }
-        if world == 1 and not args.no_cpu_baseline:
-            sd = {}
-            for sp in syn.zonos_specs(cfg):
-                t = torch.empty(sp.shape, dtype=torch.bfloat16, device=dev)
-                _lib.check(_lib.lib().zmi_fill_uniform(t.data_ptr(), sp.numel, syn.tensor_key(0, sp.name), sp.scale,
-                                                       sp.offset, 0, torch.cuda.current_stream().cuda_stream))
-                sd[sp.name] = t
-            sd["heads.0.weight"][1024] = 0
-            torch.cuda.synchronize()
-            out["cpu_baseline"] = cpu_baseline(sd, cfg)
-        else:
-            out["cpu_baseline"] = None
         print(json.dumps(out), flush=True)
     if dist:
         dist.barrier()

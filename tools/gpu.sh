@@ -74,7 +74,7 @@ case "$cmd" in
   pmc) pmc "$@" || exit $? ;;
   mfma) mfma "$@" || exit $? ;;
   round)
-    prof bench 500 python bench.py --no-cpu-baseline --no-hybrid --no-batch --no-c5 --no-default-cap || exit $?
+    prof bench 500 python bench.py --full --no-cpu-baseline --no-hybrid --no-batch --no-c5 --no-default-cap || exit $?
     pmc FETCH_SIZE attnblk attn_block_kernel 23396352 attnblk_fetch || exit $?   # QKV + out_proj + K/V at 591
     pmc WRITE_SIZE attnblk attn_block_kernel 23396352 attnblk_write || exit $?
     pmc FETCH_SIZE fc1 "gemv_kernel<2, 4, 8, 16, 1, 3, 1>" 67158016 fc1_fetch || exit $?
