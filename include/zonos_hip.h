@@ -270,6 +270,32 @@ int zmi_dac_conv_out(const void* x, int t, int c_in, const void* w_pad, const fl
                      void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Speaker encoder (Zonos.make_speaker_embedding, model.py:90-95 -> SpeakerEmbeddingLDA, speaker_cloning.py:388-412:
+ * ResNet293 with SimAM blocks). Activations are fp16 channels-last [H][W][C] (H the mel axis, W time, batch 1);
+ * conv weights fp16 channel-blocked per tap [tap = ky k + kx][Ci/32][Co][32]; fp32 accumulation on MFMA. Every
+ * reduction runs in a fixed order (no floating-point atomics): two runs give the same bits. The LDS opt-in of the
+ * conv kernel failing is an error.
+ * ------------------------------------------------------------------------------------- */
+/* Conv2d(Ci, Co, k, stride, padding = k / 2, bias = False) + eval-mode BatchNorm2d (+ ReLU) (speaker_cloning.py:69-72,
+ * 79-80, 84-85): y[ho][wo][co] = act(acc * scale[co] + shift[co]) in fp32, stored fp16; k in {1, 3}, stride in {1, 2},
+ * Ci and Co multiples of 32. psum (optional): fp32 [zmi_spk_conv2d_tiles(H, W, k, stride)][Co], the per-tile channel
+ * sums of the stored y (SimAM's mean). */
+int zmi_spk_conv2d(const void* x, int H, int W, int Ci, const void* w, const float* scale, const float* shift, int Co,
+                   int k, int stride, int relu, void* y, float* psum, void* stream);
+int zmi_spk_conv2d_tiles(int H, int W, int k, int stride);
+/* The stem, Conv2d(1, Co, 3, padding = 1) + BatchNorm2d + ReLU (speaker_cloning.py:170-171, 187): x fp16 [H][W],
+ * w fp16 [9][Co], y fp16 [H][W][Co]; a direct kernel (K = 9). */
+int zmi_spk_stem(const void* x, int H, int W, const void* w, const float* scale, const float* shift, int Co, void* y,
+                 void* stream);
+/* SimAMBasicBlock.SimAM and the block tail (speaker_cloning.py:83-96): per channel mean over H W, d = (x - mean)^2,
+ * v = sum d / (H W - 1) (two passes), y = relu(x sigmoid(d / (4 (v + 1e-4)) + 0.5) + residual); x, residual, y fp16
+ * [H][W][C] (y may be x). psum / n_psum: the producing conv's per-tile sums, or NULL / 0 (one more pass computes
+ * them). ws: >= zmi_spk_simam_ws_floats(H, W, C) floats. */
+int zmi_spk_simam(const void* x, const void* residual, int H, int W, int C, const float* psum, int n_psum, float* ws,
+                  void* y, void* stream);
+int64_t zmi_spk_simam_ws_floats(int H, int W, int C);
+
+/* ---------------------------------------------------------------------------------------
  * Prefix conditioner (Zonos.prepare_conditioning, model.py:204-212 -> PrefixConditioner.forward,
  * conditioning.py:300-310): one output row per conditioning token, then LayerNorm, bf16 out.
  * Each row names a parameter block and how to produce its d values before the LayerNorm.

@@ -142,6 +142,12 @@ _SIGS = {
     "zmi_dac_conv_t": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                 c_void_p, c_void_p]),
     "zmi_dac_conv_out": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "zmi_spk_conv2d": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                               c_void_p, c_void_p, c_void_p]),
+    "zmi_spk_conv2d_tiles": (c_int, [c_int, c_int, c_int, c_int]),
+    "zmi_spk_stem": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "zmi_spk_simam": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "zmi_spk_simam_ws_floats": (c_int64, [c_int, c_int, c_int]),
     "zmi_prefix_condition": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_float,
                                      c_void_p, c_void_p]),
     "zmi_mamba2_step": (c_int, [ctypes.POINTER(Mamba2Args), c_void_p]),

@@ -40,6 +40,8 @@ class Zonos:
         pcc = config.prefix_conditioner
         self.prefix_conditioner = (PrefixConditioner(pcc.conditioners, config.backbone.d_model, device, pcc.projection)
                                    if pcc.conditioners else None)
+        self.spk_clone_model = None      # created lazily (model.py:90-93) by make_speaker_embedding
+        self._spk_synthetic_seed = None  # Zonos.synthetic: the seed of the synthetic speaker encoder
 
     @property
     def device(self) -> torch.device:
@@ -51,6 +53,7 @@ class Zonos:
                   eos_row_scale: float | None = None, dac_seed: int = 0, **kw) -> "Zonos":
         m = cls(config, device, autoencoder=DACAutoencoder(device, seed=dac_seed), **kw)
         m.engine.init_synthetic(seed, zero_eos=zero_eos, eos_row_scale=eos_row_scale)
+        m._spk_synthetic_seed = seed
         if m.prefix_conditioner is not None:
             from . import synthetic as syn
             pcc = config.prefix_conditioner
@@ -91,6 +94,24 @@ class Zonos:
                                       max(prefill, e.max_prefill))
             self.engine.w = w
             self.engine._build_plan()
+
+    # ------------------------------------------------------------------ speaker embedding
+    def load_speaker_model(self, ckpt_path: str, lda_path: str) -> None:
+        """The published speaker encoder and its LDA (speaker_cloning.py:391-406) from local .pt / .safetensors
+        files: there is no hub download in this build."""
+        from .speaker import SpeakerEmbeddingLDA
+        self.spk_clone_model = SpeakerEmbeddingLDA.from_files(ckpt_path, lda_path, self._device)
+
+    def make_speaker_embedding(self, wav: torch.Tensor, sr: int) -> torch.Tensor:
+        """model.py:90-95: [channels, N] (or [N]) waveform at `sr` -> [1, 1, 128] bf16 for make_cond_dict(speaker=)."""
+        if self.spk_clone_model is None:
+            if self._spk_synthetic_seed is None:
+                raise RuntimeError("no speaker encoder weights: call load_speaker_model(ckpt_path, lda_path) first "
+                                   "(this build does not download them)")
+            from .speaker import SpeakerEmbeddingLDA
+            self.spk_clone_model = SpeakerEmbeddingLDA(self._device, seed=self._spk_synthetic_seed)
+        _, spk_embedding = self.spk_clone_model(wav.to(self._device), sr)
+        return spk_embedding.unsqueeze(0).bfloat16()
 
     # ------------------------------------------------------------------ conditioning
     def prepare_conditioning(self, cond_dict: dict, uncond_dict: dict | None = None) -> torch.Tensor:

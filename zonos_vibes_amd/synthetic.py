@@ -249,6 +249,55 @@ def dac_encoder_specs() -> list[Spec]:
     return out
 
 
+def speaker_block_plan(config) -> list[tuple[str, int, int, int]]:
+    """(state-dict prefix, c_in, c_out, stride) of every SimAMBasicBlock of the speaker encoder's ResNet
+    (reference speaker_cloning.py:173-184); a block has a `downsample` branch iff stride != 1 or c_in != c_out."""
+    out, c = [], config.in_planes
+    for li, n in enumerate(config.num_blocks):
+        planes = config.in_planes << li
+        for b in range(n):
+            out.append((f"front.layer{li + 1}.{b}.", c, planes, (1 if li == 0 else 2) if b == 0 else 1))
+            c = planes
+    return out
+
+
+def speaker_specs(config) -> list[Spec]:
+    """fp32 tensors of the speaker encoder (reference `ResNet293_based.state_dict()` names, speaker_cloning.py:199-224)
+    plus the LDA Linear as `lda.weight` / `lda.bias` (its own file upstream, :403-406). Conv and linear weights
+    uniform(+-1/sqrt(fan_in)); BatchNorm weight 1 +- 0.2, bias +-0.1, running_mean +-0.1, running_var 1 +- 0.2: with
+    these the full-depth network stays O(1) on a log-mel-like input, far from fp16 overflow."""
+    out = []
+
+    def conv(name, co, ci, k):
+        out.append(Spec(name + ".weight", (co, ci, k, k), "f32", 1.0 / math.sqrt(ci * k * k)))
+
+    def bn(name, c):
+        out.extend([Spec(name + ".weight", (c,), "f32", 0.2, 1.0), Spec(name + ".bias", (c,), "f32", 0.1),
+                    Spec(name + ".running_mean", (c,), "f32", 0.1), Spec(name + ".running_var", (c,), "f32", 0.2, 1.0)])
+
+    conv("front.conv1", config.in_planes, 1, 3)
+    bn("front.bn1", config.in_planes)
+    for p, ci, co, stride in speaker_block_plan(config):
+        conv(p + "conv1", co, ci, 3)
+        bn(p + "bn1", co)
+        conv(p + "conv2", co, co, 3)
+        bn(p + "bn2", co)
+        if stride != 1 or ci != co:
+            conv(p + "downsample.0", co, ci, 1)
+            bn(p + "downsample.1", co)
+    d = config.in_planes * 8 * (config.acoustic_dim // 8)
+    out += [Spec("pooling.attention.0.weight", (128, d, 1), "f32", 1.0 / math.sqrt(d)),
+            Spec("pooling.attention.0.bias", (128,), "f32", 1.0 / math.sqrt(d))]
+    bn("pooling.attention.2", 128)
+    out += [Spec("pooling.attention.3.weight", (d, 128, 1), "f32", 1.0 / math.sqrt(128)),
+            Spec("pooling.attention.3.bias", (d,), "f32", 1.0 / math.sqrt(128)),
+            Spec("bottleneck.weight", (config.embd_dim, 2 * d), "f32", 1.0 / math.sqrt(2 * d)),
+            Spec("bottleneck.bias", (config.embd_dim,), "f32", 1.0 / math.sqrt(2 * d)),
+            Spec("lda.weight", (config.lda_dim, config.embd_dim), "f32", 1.0 / math.sqrt(config.embd_dim)),
+            Spec("lda.bias", (config.lda_dim,), "f32", 1.0 / math.sqrt(config.embd_dim))]
+    return out
+
+
 def prefix_conditioner_specs(conditioners: list[dict], d: int) -> list[Spec]:
     """bf16 parameters of a PrefixConditioner (reference state-dict names under `prefix_conditioner.`,
     conditioning.py:284-291), scaled like their module inits: embeddings and Fourier weights std 1,
