@@ -233,6 +233,11 @@ int zmi_embed_codes(const int* codes, int ld_codes, int n, const void* emb, int 
 int zmi_delay_init(const ZmiSlots* slots, int slot, const int* prefix, int prefix_len, int total_len, void* stream);
 /* out[9][T] int64 = revert_delay_pattern(delayed[slot]) with >=1024 -> 0 (model.py:309-311) */
 int zmi_delay_revert(const ZmiSlots* slots, int slot, int64_t* out, int t_out, void* stream);
+/* frames t0 .. t0 + n - 1 of that result, out[9][n] int64: out[k][i] = delayed[slot][k][t0 + i + k + 1] with
+ * >=1024 -> 0 (codebook_pattern.py:9-12, model.py:309-311). Frames below offset - 9 of a running slot are final,
+ * so a streaming caller reads them before the utterance ends. Error when t0 < 0, n < 0 or t0 + n + 9 > tcap;
+ * n == 0 launches nothing. */
+int zmi_delay_revert_range(const ZmiSlots* slots, int slot, int t0, int n, int64_t* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * DAC 44.1 kHz decoder (DACAutoencoder.decode, autoencoder.py:25-27 -> transformers DacModel).
@@ -268,6 +273,10 @@ int zmi_dac_conv_t(const void* x, int t_in, int c_in, const void* w_phases, cons
  * MFMA conv kernel: w_pad fp16 [7][c_in/32][32][32] (output channel 0 = the filter, 1..31 zero), bias_pad f32 [32]. */
 int zmi_dac_conv_out(const void* x, int t, int c_in, const void* w_pad, const float* bias_pad, float* out,
                      void* stream);
+/* samples q0 .. q0 + n - 1 of that result only, out f32 [n] (the streaming decoder's crop of a window: each sample
+ * with the bits zmi_dac_conv_out gives it). Error unless 0 <= q0, 0 <= n, q0 + n <= t. */
+int zmi_dac_conv_out_range(const void* x, int t, int c_in, const void* w_pad, const float* bias_pad, int q0, int n,
+                           float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Speaker encoder (Zonos.make_speaker_embedding, model.py:90-95 -> SpeakerEmbeddingLDA, speaker_cloning.py:388-412:

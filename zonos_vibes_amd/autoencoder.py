@@ -11,6 +11,7 @@ folded to plain weights at load time.
 """
 from __future__ import annotations
 
+import ctypes
 import math
 
 import torch
@@ -18,6 +19,7 @@ import torch
 from . import _lib
 from . import synthetic as syn
 from .config import DAC_HOP, DAC_SAMPLE_RATE, N_CODEBOOKS
+from .streaming import DAC_LOOKAHEAD_FRAMES, DACStreamDecoder, dac_lookahead_frames  # noqa: F401
 
 STRIDES = syn.DAC_STRIDES
 ENC_STRIDES = syn.DAC_ENC_STRIDES
@@ -48,6 +50,65 @@ def _blocked(w: torch.Tensor) -> torch.Tensor:
     co, ci = w.shape[-2], w.shape[-1]
     assert ci % 32 == 0, ci
     return w.reshape(*w.shape[:-1], ci // 32, 32).transpose(-3, -2).contiguous().half()
+
+
+# The steady-state streaming window as one hipGraph replay instead of its 31 launches (tools/bench_stream.py
+# measures both)
+WINDOW_GRAPH = True
+
+
+class _WindowDecoder:
+    """DACStreamDecoder's decode_window on the HIP decoder: a window is decoded by _decode_one's launch sequence in
+    stage buffers of its own (a captured graph keeps their addresses), and the last stage computes only the kept
+    samples (zmi_dac_conv_out_range), so the crop costs no copy of the window and no host sync."""
+
+    def __init__(self, ae: "DACAutoencoder", chunk_frames: int, capture: bool):
+        self.ae, self.chunk, self.R, self.capture = ae, int(chunk_frames), DAC_LOOKAHEAD_FRAMES, bool(capture)
+        self.wmax = 2 * self.R + self.chunk
+        self._bufs = None
+        self._graph = None
+        self.graph_replays = 0
+
+    def _alloc(self):
+        ae = self.ae
+        self._bufs = [torch.empty(49152 * self.wmax, dtype=torch.float16, device=ae.dev) for _ in range(4)]
+        self._gcodes = torch.zeros(N_CODEBOOKS, self.wmax, dtype=torch.int64, device=ae.dev)
+        self._gout = torch.empty(DAC_HOP * self.chunk, dtype=torch.float32, device=ae.dev)
+
+    def __call__(self, codes: torch.Tensor, f0: int, f1: int) -> torch.Tensor:
+        ae = self.ae
+        W = codes.shape[1]
+        assert 0 <= f0 < f1 <= W <= self.wmax, (f0, f1, W)
+        cur = torch.cuda.current_stream(ae.dev)
+        ae.stream.wait_stream(cur)
+        with torch.cuda.stream(ae.stream):
+            if self._bufs is None:
+                self._alloc()
+            crop = (DAC_HOP * f0, DAC_HOP * (f1 - f0))
+            if self.capture and W == self.wmax and f0 == self.R and f1 == self.R + self.chunk:
+                self._gcodes.copy_(codes)
+                if self._graph is None:
+                    _lib.check(ae.lib.zmi_graph_begin(ae.sptr), "graph_begin")
+                    try:
+                        ae._decode_one(self._gcodes, self._gout, self._bufs, crop)
+                    finally:
+                        g = ctypes.c_void_p()
+                        _lib.check(ae.lib.zmi_graph_end(ae.sptr, ctypes.byref(g)), "graph_end")
+                    self._graph = g.value
+                _lib.check(ae.lib.zmi_graph_launch(self._graph, 1, ae.sptr), "graph_launch")
+                self.graph_replays += 1
+                out = self._gout.clone()
+            else:
+                out = torch.empty(crop[1], dtype=torch.float32, device=ae.dev)
+                ae._decode_one(codes.contiguous(), out, self._bufs, crop)
+        cur.wait_stream(ae.stream)
+        out.record_stream(cur)
+        return out.view(1, 1, -1)
+
+    def __del__(self):
+        if getattr(self, "_graph", None):
+            self.ae.lib.zmi_graph_destroy(self._graph)
+            self._graph = None
 
 
 class DACAutoencoder:
@@ -170,10 +231,12 @@ class DACAutoencoder:
         _lib.check(self.lib.zmi_dac_conv(p(x), t_in, c_in, p(w), p(b), c_out, taps, step, off, n_out, stride, phase,
                                          t_out, p(skip), p(raw), p(snake), p(alpha), p(f32), self.sptr), "dac_conv")
 
-    def _decode_one(self, codes: torch.Tensor, out: torch.Tensor):
-        """codes [9, T] int64 (device) -> out [512 T] fp32 (modeling_dac.py:347-371, 407-441)."""
+    def _decode_one(self, codes: torch.Tensor, out: torch.Tensor, bufs=None, crop=None):
+        """codes [9, T] int64 (device) -> out [512 T] fp32 (modeling_dac.py:347-371, 407-441).
+        bufs: the four stage buffers (default: the decoder's own, grown to T). crop = (q0, n): only samples
+        q0 .. q0 + n - 1 are computed by the last stage, into out [n] (the streaming decoder's window crop)."""
         T = codes.shape[-1]
-        H, SA, SB, S2 = self._buffers(T)
+        H, SA, SB, S2 = self._buffers(T) if bufs is None else bufs
         z = S2
         _lib.check(self.lib.zmi_dac_from_codes(codes.data_ptr(), T, self.codebooks.data_ptr(), self.proj_w.data_ptr(),
                                                self.proj_b.data_ptr(), z.data_ptr(), self.sptr), "from_codes")
@@ -206,6 +269,11 @@ class DACAutoencoder:
                            raw=None if last_unit else H, snake=xalt, alpha=nxt)
             t = tn
             xin, xalt = xalt, xin
+        if crop is not None:
+            _lib.check(self.lib.zmi_dac_conv_out_range(xin.data_ptr(), t, self.blocks[-1]["cout"],
+                                                       self.out_w.data_ptr(), self.out_b.data_ptr(), crop[0], crop[1],
+                                                       out.data_ptr(), self.sptr), "conv_out_range")
+            return
         _lib.check(self.lib.zmi_dac_conv_out(xin.data_ptr(), t, self.blocks[-1]["cout"], self.out_w.data_ptr(),
                                              self.out_b.data_ptr(), out.data_ptr(), self.sptr), "conv_out")
 
@@ -223,6 +291,13 @@ class DACAutoencoder:
                 self._decode_one(codes[b], out[b, 0])
         cur.wait_stream(self.stream)
         return out
+
+    def stream_decoder(self, chunk_frames: int = 16, capture: bool | None = None) -> DACStreamDecoder:
+        """An incremental decoder: push() code frames as they become final, flush() at the end; the concatenated
+        returns are bit for bit decode() of all the codes (streaming.py). capture: replay the steady-state window
+        (lookahead + chunk_frames + lookahead frames) as one hipGraph (default: WINDOW_GRAPH)."""
+        win = _WindowDecoder(self, chunk_frames, WINDOW_GRAPH if capture is None else capture)
+        return DACStreamDecoder(win, chunk_frames, DAC_LOOKAHEAD_FRAMES, device=self.dev)
 
     # --------------------------------------------------------------- encode
     def preprocess(self, wav: torch.Tensor, sr: int) -> torch.Tensor:

@@ -945,6 +945,22 @@ extern "C" int zmi_dac_conv_out(const void* x, int t, int c_in, const void* w_pa
   return 0;
 }
 
+extern "C" int zmi_dac_conv_out_range(const void* x, int t, int c_in, const void* w_pad, const float* bias_pad, int q0,
+                                      int n, float* out, void* stream) {
+  // zmi_dac_conv_out for samples q0 .. q0 + n - 1 only, written to out[0 .. n): the conv's input offset moves by q0,
+  // so each sample has the K order (channel step, tap) and the MFMA chain it has in the whole-length launch (the
+  // streaming decoder's crop: a window's halo samples are never computed by the last, longest stage)
+  if (c_in % 32) return zmi_fail_msg("dac_conv_out_range: c_in % 32");
+  if (q0 < 0 || n < 0 || (long)q0 + n > t) return zmi_fail_msg("dac_conv_out_range: bounds");
+  if (n == 0) return 0;
+  ConvArgs a{(const f16_t*)x, t, c_in, (const f16_t*)w_pad, bias_pad, 32, 7, 1, q0 - 3, n, 1, 0, n,
+             nullptr, nullptr, nullptr, nullptr, out, 1, 1, 0, 0};
+  const int rc = launch_conv(a, (hipStream_t)stream);
+  if (rc) return rc;
+  ZMI_CHECK(hipGetLastError());
+  return 0;
+}
+
 extern "C" int zmi_dac_conv_t(const void* x, int t_in, int c_in, const void* w_phases, const float* bias, int c_out,
                               int stride, int pad, void* out_raw, void* out_snake, const float* alpha, void* stream) {
   // ConvTranspose1d(c_in, c_out, k = 2 stride, stride, padding = pad) (modeling_dac.py:222-240) in polyphase

@@ -606,6 +606,15 @@ __global__ void delay_revert_kernel(const ZmiSlots sl, int slot, int64_t* out, i
   out[(size_t)k * t_out + t] = v >= 1024 ? 0 : v;
 }
 
+// frames t0 .. t0 + n - 1 of the reverted buffer (delay_revert_kernel's arithmetic on a range): every frame below
+// offset - 9 of a running slot is final, so a streaming caller reads them while the utterance is still generated
+__global__ void delay_revert_range_kernel(const ZmiSlots sl, int slot, int t0, int n, int64_t* out) {
+  const int i = blockIdx.x * 256 + threadIdx.x, k = blockIdx.y;
+  if (i >= n) return;
+  const int v = sl.delayed[((size_t)slot * ZMI_NCB + k) * sl.tcap + t0 + i + k + 1];
+  out[(size_t)k * n + i] = v >= 1024 ? 0 : v;
+}
+
 // standalone apply / revert over [B][9][T] int64 tensors (codebook_pattern.py:5-12)
 __global__ void apply_delay_kernel(const int64_t* codes, int64_t* out, int T, int64_t mask) {
   const int t = blockIdx.x * 256 + threadIdx.x, k = blockIdx.y, b = blockIdx.z;
@@ -739,6 +748,16 @@ extern "C" int zmi_delay_revert(const ZmiSlots* slots, int slot, int64_t* out, i
   if (t_out + ZMI_NCB > slots->tcap) return zmi_fail_msg("delay_revert: bounds");
   hipLaunchKernelGGL(delay_revert_kernel, dim3((t_out + 255) / 256, ZMI_NCB), dim3(256), 0, (hipStream_t)stream,
                      *slots, slot, out, t_out);
+  ZMI_CHECK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int zmi_delay_revert_range(const ZmiSlots* slots, int slot, int t0, int n, int64_t* out, void* stream) {
+  if (slot < 0 || slot >= slots->n_slots) return zmi_fail_msg("delay_revert_range: slot");
+  if (t0 < 0 || n < 0 || (long)t0 + n + ZMI_NCB > slots->tcap) return zmi_fail_msg("delay_revert_range: bounds");
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(delay_revert_range_kernel, dim3((n + 255) / 256, ZMI_NCB), dim3(256), 0, (hipStream_t)stream,
+                     *slots, slot, t0, n, out);
   ZMI_CHECK(hipGetLastError());
   return 0;
 }

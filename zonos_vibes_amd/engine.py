@@ -84,6 +84,16 @@ class SamplingParams:
                              int(self.repetition_penalty_window), self.seed & ((1 << 64) - 1))
 
 
+ST_FIELDS = ("active", "pos", "offset", "remaining", "stopping", "step", "total_len")  # HipEngine.st / st_all rows
+
+
+def codes_count(stt: dict) -> int:
+    """Frames read_codes returns for a slot state: the reference's `[..., :offset - 9]` of the P + N reverted frames."""
+    n_audio = stt["total_len"] - 9
+    k = stt["offset"] - 9  # python slice end `[..., :offset - 9]`, negative when stopped early by a callback
+    return min(k, n_audio) if k >= 0 else max(n_audio + k, 0)
+
+
 def _round8(n: int) -> int:
     return n if n % 8 == 0 else n + 8 - n % 8
 
@@ -234,8 +244,9 @@ class HipEngine:
             self.splitk_part = z(self.lib.zmi_gemv_splitk_floats(max(R, self.pre_rows), d), dt=torch.float32)
             self.samp_cnt = z(S, dt=torch.int32)
             self.next_tok = z(S, N_CODEBOOKS, dt=torch.int32)
-            self.st = {k: z(S, dt=torch.int32) for k in
-                       ("active", "pos", "offset", "remaining", "stopping", "step", "total_len")}
+            # the slots' loop state, one row per field, so a streaming caller reads a slot's with one copy (snapshot)
+            self.st_all = z(len(ST_FIELDS), S, dt=torch.int32)
+            self.st = {k: self.st_all[i] for i, k in enumerate(ST_FIELDS)}
             self.delayed = torch.full((S, N_CODEBOOKS, self.tcap), 1025, dtype=torch.int32, device=dev)
             self.params = z(S * ctypes.sizeof(_lib.Sampling), dt=torch.uint8)
             P2 = self.pre_rows
@@ -763,16 +774,39 @@ class HipEngine:
 
     def read_codes(self, slot: int) -> torch.Tensor:
         """revert_delay_pattern, >=1024 -> 0, truncate to offset-9 (model.py:309-311) -> [1, 9, T] int64."""
-        stt = self.slot_state(slot)
-        n_audio = stt["total_len"] - 9
-        k = stt["offset"] - 9  # python slice end `[..., :offset - 9]`, negative when stopped early by a callback
-        t = min(k, n_audio) if k >= 0 else max(n_audio + k, 0)
+        t = codes_count(self.slot_state(slot))
         with torch.cuda.stream(self.stream):
             out = torch.zeros(N_CODEBOOKS, t, dtype=torch.int64, device=self.dev)
             if t:
                 _lib.check(self.lib.zmi_delay_revert(ctypes.byref(self.slots), slot, out.data_ptr(), t, self.sptr),
                            "revert")
         self.stream.synchronize()
+        return out.unsqueeze(0)
+
+    SNAPSHOT_INTS = len(ST_FIELDS) + 3
+
+    def snapshot(self, slot: int, host: torch.Tensor) -> torch.cuda.Event:
+        """The slot's state fields (ST_FIELDS order: one small device-to-host copy) and the three error words
+        check_errors() reads, into `host` (pinned int32 [SNAPSHOT_INTS]), asynchronously on the engine's stream; the
+        returned event marks their completion. A caller that finds an error word set calls check_errors()."""
+        n = len(ST_FIELDS)
+        with torch.cuda.stream(self.stream):
+            host[:n].copy_(self.st_all[:, slot], non_blocking=True)
+            host[n: n + 1].copy_(self.attn_work[:4].view(torch.int32), non_blocking=True)
+            host[n + 1: n + 3].copy_(self.blk_err[:2], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(self.stream)
+        return ev
+
+    def read_final_codes(self, slot: int, t0: int, t1: int) -> torch.Tensor:
+        """Frames t0 .. t1 - 1 of read_codes' result -> [1, 9, t1 - t0] int64, enqueued on the engine's stream with no
+        host sync: the caller orders its consumer after the stream (an event) and reads only frames that are final
+        (below offset - 9 while the slot runs, read_codes' count once it has stopped)."""
+        n = t1 - t0
+        with torch.cuda.stream(self.stream):
+            out = torch.empty(N_CODEBOOKS, max(n, 0), dtype=torch.int64, device=self.dev)
+            _lib.check(self.lib.zmi_delay_revert_range(ctypes.byref(self.slots), slot, t0, n, out.data_ptr(),
+                                                       self.sptr), "revert_range")
         return out.unsqueeze(0)
 
     def release(self, slot: int):

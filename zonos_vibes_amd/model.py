@@ -3,6 +3,7 @@
     model = Zonos.synthetic(zonos_v01_transformer(), device="cuda")      # or Zonos.from_local(...)
     codes = model.generate(prefix_conditioning)                          # [1, 9, T] int64
     wav = model.autoencoder.decode(codes)                                # [1, 1, 512 T] fp32
+    for wav in model.stream(prefix_conditioning): ...                    # the same samples, in chunks, as they are ready
 
 `generate` keeps the reference's arguments and batch_size=1 semantics; `generate_batch`
 runs many independent utterances through the slots of one engine (continuous batching at
@@ -19,7 +20,7 @@ from . import _lib  # noqa: F401  (fail loudly at import if the HIP library is m
 from .autoencoder import DACAutoencoder
 from .conditioning import PrefixConditioner
 from .config import N_CODEBOOKS, ZonosConfig
-from .engine import SamplingParams, make_engine
+from .engine import ST_FIELDS, SamplingParams, codes_count, make_engine
 
 
 def _draw_seed() -> int:
@@ -42,6 +43,13 @@ class Zonos:
                                    if pcc.conditioners else None)
         self.spk_clone_model = None      # created lazily (model.py:90-93) by make_speaker_embedding
         self._spk_synthetic_seed = None  # Zonos.synthetic: the seed of the synthetic speaker encoder
+        self._stream_decoders: dict = {}  # stream(): one DACStreamDecoder per chunk_frames
+        # stream(): True lets the DAC windows run beside the next decode steps. Measured: the decode
+        # step's codes are then not reproducible (a few utterances in ten diverge from generate() at some frame), so
+        # the windows run between the rounds of steps instead and stream() is exact. tools/bench_stream.py sets it to
+        # time the overlapped form.
+        self._stream_overlap = False
+        self._stream_glue = None
 
     @property
     def device(self) -> torch.device:
@@ -174,6 +182,107 @@ class Zonos:
         out = e.read_codes(slot)
         e.release(slot)
         return out
+
+    @torch.inference_mode()
+    def stream(self, prefix_conditioning: torch.Tensor, audio_prefix_codes: torch.Tensor | None = None,
+               max_new_tokens: int = 86 * 30, cfg_scale: float = 2.0, sampling_params: dict = dict(min_p=0.1),
+               chunk_frames: int = 16):
+        """generate() + autoencoder.decode() as a generator of waveform chunks [1, 1, 512 n] fp32 (device): audio
+        is yielded while the utterance is still being generated. With the same torch.manual_seed, the chunks
+        concatenated are bit for bit decode(generate(...)) (batch 1, generate()'s arguments).
+
+        A frame is final once the delayed buffer's column frame + 9 is written; it is decoded once the DAC decoder's
+        lookahead (DAC_LOOKAHEAD_FRAMES) beyond it is final too. A round is `chunk_frames` decode steps on the engine's
+        stream, the read of the frames they make final, and those frames' DAC windows on the autoencoder's stream,
+        all enqueued one round ahead of the host and ordered by events; the host waits only for a round's one small
+        state copy before it yields the round's audio."""
+        assert cfg_scale != 1, "TODO: add support for cfg_scale=1"
+        if prefix_conditioning.shape[0] != 2:
+            raise ValueError("stream() has generate()'s batch_size=1 semantics: prefix_conditioning [2, Lc, d]")
+        if chunk_frames < 1:
+            raise ValueError("chunk_frames >= 1")
+        lc = prefix_conditioning.shape[1]
+        p = 0 if audio_prefix_codes is None else audio_prefix_codes.shape[2]
+        self._ensure_capacity(1, lc + p + max_new_tokens + 9, lc + p + 1)
+        e = self.engine
+        params = SamplingParams.from_dict(dict(sampling_params), cfg_scale, _draw_seed())
+        slot = 0
+        key = (id(self.autoencoder), int(chunk_frames))
+        if key not in self._stream_decoders:  # kept: its window graph and stage buffers serve every later call
+            self._stream_decoders[key] = self.autoencoder.stream_decoder(chunk_frames)
+        dec = self._stream_decoders[key]
+        dec._reset()  # (an earlier stream closed before its end)
+        n_audio, max_steps = p + max_new_tokens, max_new_tokens + 8
+        host = [torch.empty(e.SNAPSHOT_INTS, dtype=torch.int32).pin_memory() for _ in range(2)]
+        cur = torch.cuda.current_stream(self._device)
+        if self._stream_glue is None:
+            self._stream_glue = torch.cuda.Stream(self._device)
+        # the rounds' decoder calls are enqueued ahead of the host on a stream of their own: the caller's stream waits
+        # only for the chunk it is handed, not for the round already in flight behind it
+        glue = self._stream_glue
+        steps = read_to = rounds = 0
+
+        def launch(n: int):
+            """Enqueue n more decode steps, the read of the frames they make final, the slot's state copy, and the
+            DAC windows of those frames. After `steps` steps a running slot's offset is p + 1 + steps, so the frames
+            are known on the host before the steps have run; if the state copy later shows that the slot stopped
+            within these steps (EOS countdown), fewer frames count and the decoder is rolled back to `saved`."""
+            nonlocal steps, read_to, rounds
+            if n:
+                if not self._stream_overlap:
+                    e.stream.wait_stream(ae.stream)  # the previous round's windows first (see _stream_overlap)
+                e.step(n, slots=1)
+                steps += n
+            t0, t1 = read_to, max(min(p + 1 + steps - 9, n_audio), read_to)
+            codes = e.read_final_codes(slot, t0, t1)
+            h = host[rounds & 1]
+            rounds += 1
+            read_to = t1
+            ev = e.snapshot(slot, h)
+            saved = dec._state()
+            with torch.cuda.stream(glue):
+                glue.wait_event(ev)
+                if t1 > t0:
+                    codes.record_stream(glue)
+                wav = dec.push(codes)
+                ready = torch.cuda.Event()
+                ready.record(glue)
+            return codes, t0, t1, h, ev, saved, wav, ready
+
+        ae = self.autoencoder
+        try:
+            e.prefill(slot, prefix_conditioning, audio_prefix_codes, max_new_tokens, params)
+            queue = [launch(0)]  # audio-prefix frames are final before any decode step
+            while queue:
+                if steps < max_steps:  # keep the engine one round ahead of the host
+                    queue.append(launch(min(chunk_frames, max_steps - steps)))
+                codes, t0, t1, h, ev, saved, wav, ready = queue.pop(0)
+                ev.synchronize()
+                vals = h.tolist()
+                if any(vals[len(ST_FIELDS):]):  # the words check_errors() reads, copied with the state
+                    e.check_errors()
+                stt = dict(zip(ST_FIELDS, vals))
+                if stt["active"]:
+                    if t1 > t0 and stt["offset"] - 9 < t1:
+                        raise RuntimeError("stream: the slot's offset is behind the steps enqueued")
+                else:  # ended (EOS countdown or max_new_tokens): read_codes' count, then the decoder's tail
+                    good = min(codes_count(stt), t1)
+                    with torch.cuda.stream(glue):
+                        if good < t1 or queue:  # the rounds decoded past the end are dropped
+                            dec._restore(saved)
+                            wav = dec.push(codes[..., :max(good - t0, 0)])
+                        queue.clear()
+                        tail = dec.flush()
+                        wav = tail if wav.shape[-1] == 0 else torch.cat([wav, tail], dim=-1)
+                        ready = torch.cuda.Event()
+                        ready.record(glue)
+                if wav.shape[-1]:
+                    cur.wait_event(ready)
+                    wav.record_stream(cur)
+                    yield wav
+        finally:
+            dec._reset()
+            e.release(slot)
 
     @torch.inference_mode()
     def generate_batch(self, conds: Sequence[torch.Tensor], prefixes: Sequence[torch.Tensor | None] | None = None,
