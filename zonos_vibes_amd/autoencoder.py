@@ -52,6 +52,62 @@ def _blocked(w: torch.Tensor) -> torch.Tensor:
     return w.reshape(*w.shape[:-1], ci // 32, 32).transpose(-3, -2).contiguous().half()
 
 
+def pack_conv(w: torch.Tensor) -> torch.Tensor:
+    """Conv1d weight [co][ci][k] -> what zmi_dac_conv reads: channel-blocked [k][ci / 32][co][32] fp16 (_blocked),
+    or [1][co][ci] for a 1x1 conv."""
+    w = w.to(torch.float32).permute(2, 0, 1)
+    return w.contiguous().half() if w.shape[0] == 1 else _blocked(w)
+
+
+def pack_conv_transpose(wt: torch.Tensor, stride: int, pad: int) -> torch.Tensor:
+    """ConvTranspose1d(k = 2 stride, stride, padding = pad) weight [ci][co][2 stride] -> zmi_dac_conv_t's polyphase
+    weights [stride][2][ci / 32][co][32] fp16: phase rho uses taps (rho + pad) % stride and + stride, transposed."""
+    wt = wt.to(torch.float32)
+    assert wt.shape[2] == 2 * stride, (wt.shape, stride)
+    phases = []
+    for rho in range(stride):
+        k0 = (rho + pad) % stride
+        phases.append(torch.stack([wt[:, :, k0].t(), wt[:, :, k0 + stride].t()]))  # [2][cout][cin]
+    return _blocked(torch.stack(phases))
+
+
+def pack_strided_conv(wt: torch.Tensor, stride: int, pad: int) -> torch.Tensor:
+    """Conv1d(c, co, k = 2 s, stride s, padding = pad) weight [co][c][2 s] -> a stride-1, 3-tap conv (in_off -1) over
+    the polyphase view x'[t][j*c + ci] = x[s t + j][ci]: out[t] = sum_{a=-1..1} W'[a] x'[t + a] with
+    W'[a][co][j*c + ci] = W[co][ci][s a + j + pad] (0 if that tap is outside [0, 2s)); blocked [3][s c / 32][co][32]."""
+    wt = wt.to(torch.float32)
+    co, c, k2 = wt.shape
+    s = stride
+    assert k2 == 2 * s, (wt.shape, stride)
+    wp = torch.zeros(3, co, s, c, device=wt.device)
+    for a in range(3):
+        for jj in range(s):
+            k = s * (a - 1) + jj + pad
+            if 0 <= k < 2 * s:
+                wp[a, :, jj, :] = wt[:, :, k]
+    return _blocked(wp.reshape(3, co, s * c))
+
+
+def pack_conv_out(w2: torch.Tensor, b2: torch.Tensor):
+    """decoder.conv2 (Conv1d(ci, 1, k7)) weight [1][ci][7] and bias [1] -> zmi_dac_conv_out's 32-channel tile:
+    weights [7][ci / 32][32][32] fp16 with output channel 0 the filter and 1..31 zero, bias f32 [32]."""
+    w2 = w2.to(torch.float32)
+    w = torch.zeros(w2.shape[2], 32, w2.shape[1], device=w2.device)  # [k][co padded to 32][ci]
+    w[:, 0, :] = w2[0].t()
+    b = torch.zeros(32, device=w2.device)
+    b[0] = b2.to(torch.float32).reshape(-1)[0]
+    return _blocked(w), b
+
+
+def pack_im2col_conv1(w1: torch.Tensor) -> torch.Tensor:
+    """encoder.conv1 (Conv1d(1, co, k7)) weight [co][1][7] -> the 1x1 weight [1][co][32] fp16 over zmi_dac_im2col7's
+    rows (taps 0..6 in columns 0..6, the rest zero)."""
+    w1 = w1.to(torch.float32)
+    col = torch.zeros(1, w1.shape[0], 32, device=w1.device)
+    col[0, :, :w1.shape[2]] = w1[:, 0, :]
+    return col.half().contiguous()
+
+
 # The steady-state streaming window as one hipGraph replay instead of its 31 launches (tools/bench_stream.py
 # measures both; DESIGN.md §5g)
 WINDOW_GRAPH = True
@@ -136,9 +192,8 @@ class DACAutoencoder:
     def _prepare(self, sd: dict):
         f32 = lambda t: t.to(self.dev, torch.float32).contiguous()  # noqa: E731
 
-        def conv_w(w):  # [co][ci][k] -> channel-blocked [k][ci / 32][co][32] fp16 (_blocked); 1x1: [1][co][ci]
-            w = w.to(self.dev, torch.float32).permute(2, 0, 1)
-            return w.contiguous().half() if w.shape[0] == 1 else _blocked(w)
+        def conv_w(w):  # [co][ci][k] -> channel-blocked [k][ci / 32][co][32] fp16; 1x1: [1][co][ci]
+            return pack_conv(w.to(self.dev))
 
         with torch.cuda.stream(self.stream):
             q = "quantizer.quantizers."
@@ -153,13 +208,9 @@ class DACAutoencoder:
                 p = f"decoder.block.{j}."
                 wt = sd[p + "conv_t1.weight"].to(self.dev, torch.float32)  # [cin][cout][2s]
                 pad = math.ceil(s / 2)
-                phases = []
-                for rho in range(s):  # polyphase: phase rho uses taps (rho + pad) % s and + s, transposed
-                    k0 = (rho + pad) % s
-                    phases.append(torch.stack([wt[:, :, k0].t(), wt[:, :, k0 + s].t()]))  # [2][cout][cin]
                 blk = dict(stride=s, pad=pad, cin=wt.shape[0], cout=wt.shape[1],
                            alpha=f32(sd[p + "snake1.alpha"]).reshape(-1),
-                           wt=_blocked(torch.stack(phases)), bt=f32(sd[p + "conv_t1.bias"]), res=[])
+                           wt=pack_conv_transpose(wt, s, pad), bt=f32(sd[p + "conv_t1.bias"]), res=[])
                 for u in range(3):
                     r = p + f"res_unit{u + 1}."
                     blk["res"].append(dict(a1=f32(sd[r + "snake1.alpha"]).reshape(-1),
@@ -168,12 +219,8 @@ class DACAutoencoder:
                                            w2=conv_w(sd[r + "conv2.weight"]), b2=f32(sd[r + "conv2.bias"])))
                 self.blocks.append(blk)
             self.final_alpha = f32(sd["decoder.snake1.alpha"]).reshape(-1)
-            w2 = f32(sd["decoder.conv2.weight"])                              # [1][96][7]
-            self.out_w = torch.zeros(7, 32, w2.shape[1], device=self.dev)     # [k][co padded to 32][ci]
-            self.out_w[:, 0, :] = w2[0].t()
-            self.out_w = _blocked(self.out_w)
-            self.out_b = torch.zeros(32, device=self.dev)
-            self.out_b[0] = f32(sd["decoder.conv2.bias"]).reshape(-1)[0]
+            self.out_w, self.out_b = pack_conv_out(f32(sd["decoder.conv2.weight"]),   # [1][96][7]
+                                                   f32(sd["decoder.conv2.bias"]))
             self.has_encoder = "encoder.conv1.weight" in sd
             if self.has_encoder:
                 self._prepare_encoder(sd, f32, conv_w)
@@ -181,9 +228,7 @@ class DACAutoencoder:
 
     def _prepare_encoder(self, sd, f32, conv_w):
         w1 = f32(sd["encoder.conv1.weight"])                                  # [64][1][7]
-        col = torch.zeros(1, w1.shape[0], 32, device=self.dev)
-        col[0, :, :7] = w1[:, 0, :]
-        self.e1_w, self.e1_b = col.half().contiguous(), f32(sd["encoder.conv1.bias"])  # 1x1: [1][co][ci]
+        self.e1_w, self.e1_b = pack_im2col_conv1(w1), f32(sd["encoder.conv1.bias"])    # 1x1: [1][co][ci]
         self.eblocks = []
         c = w1.shape[0]
         for j, s in enumerate(ENC_STRIDES):
@@ -193,19 +238,11 @@ class DACAutoencoder:
                         a2=f32(sd[p + f"res_unit{u + 1}.snake2.alpha"]).reshape(-1),
                         w2=conv_w(sd[p + f"res_unit{u + 1}.conv2.weight"]), b2=f32(sd[p + f"res_unit{u + 1}.conv2.bias"]))
                    for u in range(3)]
-            # Conv1d(c, 2c, k=2s, stride s, pad ceil(s/2)) over the polyphase view x'[t][j*c + ci] = x[s t + j][ci]:
-            # out[t] = sum_{a=-1..1} W'[a] x'[t + a] with W'[a][co][j*c + ci] = W[co][ci][s a + j + pad] (0 if
-            # that tap is outside [0, 2s)) -- a stride-1, 3-tap conv with c_in = s*c
+            # Conv1d(c, 2c, k=2s, stride s, pad ceil(s/2)) as a stride-1, 3-tap conv with c_in = s*c over the
+            # polyphase view of its input (pack_strided_conv)
             wt = f32(sd[p + "conv1.weight"])                                   # [2c][c][2s]
-            pad = math.ceil(s / 2)
-            wp = torch.zeros(3, 2 * c, s, c, device=self.dev)
-            for a in range(3):
-                for jj in range(s):
-                    k = s * (a - 1) + jj + pad
-                    if 0 <= k < 2 * s:
-                        wp[a, :, jj, :] = wt[:, :, k]
             self.eblocks.append(dict(stride=s, c=c, res=res, alpha=f32(sd[p + "snake1.alpha"]).reshape(-1),
-                                     w=_blocked(wp.reshape(3, 2 * c, s * c)), b=f32(sd[p + "conv1.bias"])))
+                                     w=pack_strided_conv(wt, s, math.ceil(s / 2)), b=f32(sd[p + "conv1.bias"])))
             c *= 2
         self.e_final_alpha = f32(sd["encoder.snake1.alpha"]).reshape(-1)
         self.e2_w, self.e2_b = conv_w(sd["encoder.conv2.weight"]), f32(sd["encoder.conv2.bias"])
