@@ -277,6 +277,27 @@ int zmi_dac_conv_out(const void* x, int t, int c_in, const void* w_pad, const fl
  * with the bits zmi_dac_conv_out gives it). Error unless 0 <= q0, 0 <= n, q0 + n <= t. */
 int zmi_dac_conv_out_range(const void* x, int t, int c_in, const void* w_pad, const float* bias_pad, int q0, int n,
                            float* out, void* stream);
+/* The decoder's entry points over `lanes` independent utterances of one shape in one launch (the batched streaming
+ * window, DACAutoencoder._decode_lanes): the arguments of the single-utterance entry point, then lanes and, for every
+ * activation buffer the call touches, its lane stride in elements (lane l's buffer starts l strides after the
+ * pointer given; codes int64 [9][T] per lane). Weights, bias and alpha are shared; t_in, n_out and the crop are the
+ * same for every lane. A lane is a pointer offset (grid z = lane * phases + phase): each output element has the K
+ * order and MFMA chain the single-utterance launch gives it, so the bits are the same, and rows outside a lane's
+ * [0, t_in) are zeros, never a neighbour's data. The tile choice counts every lane's workgroups. The single entry
+ * points are these with lanes = 1 (strides ignored). Error (no launch) when lanes < 1, when lanes > 1 and a present
+ * buffer's stride is smaller than one lane's extent (t_in c_in for x, t_out c_out for skip / raw / snake / f32, n
+ * for conv_out_range's out, 9 T for codes, 1024 T for z), or when lanes * phases (from_codes: lanes) > 65535. */
+int zmi_dac_from_codes_lanes(const int64_t* codes, int T, const float* codebooks, const float* proj_w,
+                             const float* proj_b, void* z, int lanes, int64_t ls_codes, int64_t ls_z, void* stream);
+int zmi_dac_conv_lanes(const void* x, int t_in, int c_in, const void* w, const float* bias, int c_out, int taps,
+                       int tap_step, int in_off, int n_out, int out_stride, int out_phase, int t_out, const void* skip,
+                       void* out_raw, void* out_snake, const float* alpha, float* out_f32, int lanes, int64_t ls_x,
+                       int64_t ls_skip, int64_t ls_raw, int64_t ls_snake, int64_t ls_f32, void* stream);
+int zmi_dac_conv_t_lanes(const void* x, int t_in, int c_in, const void* w_phases, const float* bias, int c_out,
+                         int stride, int pad, void* out_raw, void* out_snake, const float* alpha, int lanes,
+                         int64_t ls_x, int64_t ls_raw, int64_t ls_snake, void* stream);
+int zmi_dac_conv_out_range_lanes(const void* x, int t, int c_in, const void* w_pad, const float* bias_pad, int q0,
+                                 int n, float* out, int lanes, int64_t ls_x, int64_t ls_out, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Speaker encoder (Zonos.make_speaker_embedding, model.py:90-95 -> SpeakerEmbeddingLDA, speaker_cloning.py:388-412:
@@ -406,7 +427,7 @@ int zmi_graph_destroy(void* graph_exec);
 const char* zmi_last_error(void);
 /* ABI version, bumped whenever a weight layout or an option's meaning changes: 4 = channel-blocked DAC conv weights
  * [tap][ci / 32][co][32] (zmi_dac_conv / conv_t / conv_out) and the round-5 ZMI_OPT_GEMM_ROWS bits; 5 =
- * ZMI_OPT_XC_HANDOFF and zmi_xcd_dealing; 6 = ZMI_PRO_GRMS_G and ZmiMamba2Args.gz_g. Check it before packing weights (zonos_vibes_amd/_lib.py refuses a library
+ * ZMI_OPT_XC_HANDOFF and zmi_xcd_dealing; 6 = ZMI_PRO_GRMS_G and ZmiMamba2Args.gz_g; 7 = the zmi_dac_*_lanes entry points. Check it before packing weights (zonos_vibes_amd/_lib.py refuses a library
  * whose version differs). */
 int zmi_version(void);
 /* 1 if this device deals a launch's workgroups round-robin over its XCDs (blocks b and b + 8 on one XCD, 8

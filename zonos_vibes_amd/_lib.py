@@ -137,6 +137,15 @@ _SIGS = {
     "zmi_dac_from_codes": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "zmi_dac_conv": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                              c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "zmi_dac_from_codes_lanes": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64,
+                                         c_int64, c_void_p]),
+    "zmi_dac_conv_lanes": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                   c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64,
+                                   c_int64, c_int64, c_int64, c_int64, c_void_p]),
+    "zmi_dac_conv_t_lanes": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                     c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p]),
+    "zmi_dac_conv_out_range_lanes": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
+                                             c_int64, c_int64, c_void_p]),
     "zmi_dac_im2col7": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     "zmi_dac_vq": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                            c_void_p, c_void_p]),
@@ -178,7 +187,7 @@ _SIGS = {
 
 EXPORTED = sorted(_SIGS)
 _lib = None
-ABI_VERSION = 6  # zmi_version() of the library this binding (and its weight packers) is written for
+ABI_VERSION = 7  # zmi_version() of the library this binding (and its weight packers) is written for
 
 
 def load(path: str = LIB_PATH) -> ctypes.CDLL:

@@ -19,7 +19,8 @@ import torch
 from . import _lib
 from . import synthetic as syn
 from .config import DAC_HOP, DAC_SAMPLE_RATE, N_CODEBOOKS
-from .streaming import DAC_LOOKAHEAD_FRAMES, DACStreamDecoder, dac_lookahead_frames  # noqa: F401
+from .streaming import (DAC_LOOKAHEAD_FRAMES, DACBatchStreamDecoder, DACStreamDecoder,  # noqa: F401
+                        dac_lookahead_frames)
 
 STRIDES = syn.DAC_STRIDES
 ENC_STRIDES = syn.DAC_ENC_STRIDES
@@ -165,6 +166,68 @@ class _WindowDecoder:
         if getattr(self, "_graph", None):
             self.ae.lib.zmi_graph_destroy(self._graph)
             self._graph = None
+
+
+STAGE_HALFS_PER_FRAME = 49152  # max over stages of C x time per code frame (blocks 3 and 4: 192 x 256 = 96 x 512)
+
+
+class _BatchWindowDecoder:
+    """DACBatchStreamDecoder's decode_windows on the HIP decoder: the windows of a call are grouped by shape
+    (W, f0, f1) and each group of two or more is ONE _decode_lanes launch sequence over all its lanes (a group of
+    one goes through _WindowDecoder, the single-utterance path stream() runs). Stage buffers hold the lanes in use
+    and grow on demand. The launches are not captured: a graph per lane count measured no faster on the wall at any
+    lane count (7.35 ms replayed against 7.18 ms launched at 64 lanes), and without one a group
+    decodes exactly its lanes, with no padding to a captured size."""
+
+    def __init__(self, ae: "DACAutoencoder", max_lanes: int, chunk_frames: int):
+        self.ae, self.max_lanes, self.chunk, self.R = ae, int(max_lanes), int(chunk_frames), DAC_LOOKAHEAD_FRAMES
+        self.wmax = 2 * self.R + self.chunk
+        self.single = _WindowDecoder(ae, chunk_frames, WINDOW_GRAPH)
+        self._cap = 0        # lanes the stage buffers hold
+        self._bufs = None
+        self.lane_launches = 0  # _decode_lanes launch sequences issued
+        self.lanes_decoded = 0  # windows decoded in them
+
+    def _reserve(self, lanes: int):
+        if lanes > self._cap:
+            self._bufs = None  # freed before the larger ones are allocated
+            self._bufs = [torch.empty(lanes * STAGE_HALFS_PER_FRAME * self.wmax, dtype=torch.float16, device=self.ae.dev)
+                          for _ in range(4)]
+            self._cap = lanes
+
+    def _group(self, windows, W: int, f0: int, f1: int) -> list:
+        """One shape's windows (n >= 2) -> their waveforms [1, 1, 512 (f1 - f0)], in order."""
+        n = len(windows)
+        self._reserve(n)
+        out = torch.empty(n, DAC_HOP * (f1 - f0), dtype=torch.float32, device=self.ae.dev)
+        self.ae._decode_lanes(torch.stack(windows), out, self._bufs, (DAC_HOP * f0, DAC_HOP * (f1 - f0)))
+        self.lane_launches += 1
+        self.lanes_decoded += n
+        return [out[i].view(1, 1, -1) for i in range(n)]
+
+    def __call__(self, windows: list) -> list:
+        ae = self.ae
+        groups: dict = {}
+        for i, (codes, f0, f1) in enumerate(windows):
+            W = codes.shape[1]
+            assert 0 <= f0 < f1 <= W <= self.wmax, (f0, f1, W)
+            groups.setdefault((W, f0, f1), []).append(i)
+        res = [None] * len(windows)
+        cur = torch.cuda.current_stream(ae.dev)
+        for (W, f0, f1), idx in groups.items():
+            for k in range(0, len(idx), self.max_lanes):
+                part = idx[k: k + self.max_lanes]
+                if len(part) == 1:
+                    res[part[0]] = self.single(windows[part[0]][0], f0, f1)
+                    continue
+                ae.stream.wait_stream(cur)
+                with torch.cuda.stream(ae.stream):
+                    outs = self._group([windows[i][0] for i in part], W, f0, f1)
+                cur.wait_stream(ae.stream)
+                for i, o in zip(part, outs):
+                    o.record_stream(cur)
+                    res[i] = o
+        return res
 
 
 class DACAutoencoder:
@@ -314,9 +377,67 @@ class DACAutoencoder:
         _lib.check(self.lib.zmi_dac_conv_out(xin.data_ptr(), t, self.blocks[-1]["cout"], self.out_w.data_ptr(),
                                              self.out_b.data_ptr(), out.data_ptr(), self.sptr), "conv_out")
 
+    def _decode_lanes(self, codes: torch.Tensor, out: torch.Tensor, bufs, crop=None):
+        """_decode_one over B utterances of one length in the same 31 launches (the zmi_dac_*_lanes entry points):
+        codes [B, 9, T] int64 contiguous (device) -> out [B, n] fp32 contiguous. bufs: four stage buffers of at least
+        B x 49152 T halfs each; every stage's activations are [B][t][c] dense, so a lane's stride is that stage's
+        t x c. crop = (q0, n): samples q0 .. q0 + n - 1 of every lane (default: all 512 T). Each lane's samples have
+        the bits _decode_one gives them (the lanes entry points' contract, tests/test_gpu_dac_lanes.py)."""
+        B, _, T = codes.shape
+        assert codes.is_contiguous() and out.is_contiguous() and out.shape[0] == B
+        assert all(b.numel() >= B * STAGE_HALFS_PER_FRAME * T for b in bufs)
+        H, SA, SB, S2 = bufs
+        lib, p, ck = self.lib, _lib.ptr, _lib.check
+
+        def conv(x, t_in, c_in, w, b, c_out, taps, step, off, n_out, skip=None, raw=None, snake=None, alpha=None):
+            ls_in, ls_out = t_in * c_in, n_out * c_out
+            ck(lib.zmi_dac_conv_lanes(p(x), t_in, c_in, p(w), p(b), c_out, taps, step, off, n_out, 1, 0, n_out, p(skip),
+                                      p(raw), p(snake), p(alpha), None, B, ls_in, ls_out, ls_out, ls_out, 0,
+                                      self.sptr), "dac_conv_lanes")
+
+        z = S2
+        ck(lib.zmi_dac_from_codes_lanes(codes.data_ptr(), T, self.codebooks.data_ptr(), self.proj_w.data_ptr(),
+                                        self.proj_b.data_ptr(), z.data_ptr(), B, N_CODEBOOKS * T, 1024 * T, self.sptr),
+           "from_codes_lanes")
+        conv(z, T, self.c1_cin, self.c1_w, self.c1_b, self.c1_cout, 7, 1, -3, T, snake=SA,
+             alpha=self.blocks[0]["alpha"])
+        t = T
+        xin, xalt = SA, SB
+        for j, blk in enumerate(self.blocks):
+            s, cin, cout = blk["stride"], blk["cin"], blk["cout"]
+            tn = t * s
+            res = blk["res"]
+            ck(lib.zmi_dac_conv_t_lanes(xin.data_ptr(), t, cin, blk["wt"].data_ptr(), blk["bt"].data_ptr(), cout, s,
+                                        blk["pad"], H.data_ptr(), xalt.data_ptr(), res[0]["a1"].data_ptr(), B,
+                                        t * cin, tn * cout, tn * cout, self.sptr), "dac_conv_t_lanes")
+            for u, dil in enumerate(DILATIONS):
+                ru = res[u]
+                conv(xalt, tn, cout, ru["w1"], ru["b1"], cout, 7, dil, -3 * dil, tn, snake=S2, alpha=ru["a2"])
+                last_unit = u == len(DILATIONS) - 1
+                if not last_unit:
+                    nxt = res[u + 1]["a1"]
+                elif j + 1 < len(self.blocks):
+                    nxt = self.blocks[j + 1]["alpha"]
+                else:
+                    nxt = self.final_alpha
+                conv(S2, tn, cout, ru["w2"], ru["b2"], cout, 1, 0, 0, tn, skip=H, raw=None if last_unit else H,
+                     snake=xalt, alpha=nxt)
+            t = tn
+            xin, xalt = xalt, xin
+        q0, n = (0, t) if crop is None else crop
+        assert out.shape[1] == n
+        ck(lib.zmi_dac_conv_out_range_lanes(xin.data_ptr(), t, self.blocks[-1]["cout"], self.out_w.data_ptr(),
+                                            self.out_b.data_ptr(), q0, n, out.data_ptr(), B,
+                                            t * self.blocks[-1]["cout"], n, self.sptr), "conv_out_range_lanes")
+
+    # stage memory of one decode() launch sequence over several utterances (4 buffers x 49152 T halfs per lane)
+    DECODE_LANES_BYTES = 1 << 30
+
     @torch.inference_mode()
     def decode(self, codes: torch.Tensor) -> torch.Tensor:
-        """[B, 9, T] codes -> [B, 1, 512 T] fp32 waveform (reference autoencoder.py:25-27)."""
+        """[B, 9, T] codes -> [B, 1, 512 T] fp32 waveform (reference autoencoder.py:25-27). B > 1: the utterances
+        share T, so they are lanes of one launch sequence (as many at a time as DECODE_LANES_BYTES of stage memory
+        hold), each with the bits its own decode() gives."""
         B, nq, T = codes.shape
         assert nq == N_CODEBOOKS
         out = torch.empty(B, 1, DAC_HOP * T, dtype=torch.float32, device=self.dev)
@@ -324,8 +445,14 @@ class DACAutoencoder:
         self.stream.wait_stream(cur)
         with torch.cuda.stream(self.stream):
             codes = codes.to(self.dev, torch.int64).contiguous()
-            for b in range(B):
-                self._decode_one(codes[b], out[b, 0])
+            if B == 1:
+                self._decode_one(codes[0], out[0, 0])
+            elif T > 0:
+                per = max(1, min(B, 4096, self.DECODE_LANES_BYTES // (4 * 2 * STAGE_HALFS_PER_FRAME * T)))
+                bufs = [torch.empty(per * STAGE_HALFS_PER_FRAME * T, dtype=torch.float16, device=self.dev)
+                        for _ in range(4)]
+                for b in range(0, B, per):
+                    self._decode_lanes(codes[b: b + per], out[b: b + per, 0], bufs)
         cur.wait_stream(self.stream)
         return out
 
@@ -335,6 +462,14 @@ class DACAutoencoder:
         (lookahead + chunk_frames + lookahead frames) as one hipGraph (default: WINDOW_GRAPH)."""
         win = _WindowDecoder(self, chunk_frames, WINDOW_GRAPH if capture is None else capture)
         return DACStreamDecoder(win, chunk_frames, DAC_LOOKAHEAD_FRAMES, device=self.dev)
+
+    def stream_decoder_batch(self, lanes: int, chunk_frames: int = 16) -> DACBatchStreamDecoder:
+        """`lanes` incremental decoders that decode together: push({lane: codes}) / flush(lanes) / reset(lane)
+        (streaming.DACBatchStreamDecoder); per lane the concatenated returns are bit for bit decode() of its codes. All
+        the windows of equal shape that a call makes due are lanes of one launch sequence (_decode_lanes); stage memory
+        is allocated for the lanes in use."""
+        win = _BatchWindowDecoder(self, lanes, chunk_frames)
+        return DACBatchStreamDecoder(win, lanes, chunk_frames, DAC_LOOKAHEAD_FRAMES, device=self.dev)
 
     # --------------------------------------------------------------- encode
     def preprocess(self, wav: torch.Tensor, sr: int) -> torch.Tensor:

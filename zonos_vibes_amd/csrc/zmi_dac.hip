@@ -34,7 +34,28 @@ struct ConvArgs {
   // out_phase = rho. nphase == 1: in_off / out_phase / w as given.
   int nphase, phase_pad;
   size_t w_phase;
+  // lanes: independent utterances of one shape in one launch (blockIdx.z = lane * nphase + rho). Lane l's
+  // activation buffers start ls_* elements times l after lane 0's; weights, bias and alpha are shared.
+  int lanes = 1;
+  size_t ls_x = 0, ls_skip = 0, ls_raw = 0, ls_snake = 0, ls_f32 = 0;
 };
+
+// The launch's arguments as this workgroup's lane sees them (its own activation pointers) and its phase rho. A
+// lane is a pointer offset and nothing else: rows outside [0, t_in) are zeros per lane, so no lane reads another's.
+__device__ __forceinline__ ConvArgs conv_lane_args(const ConvArgs& a0, int& rho) {
+  ConvArgs a = a0;
+  rho = blockIdx.z;
+  if (a.lanes > 1) {
+    const int l = (int)blockIdx.z / a.nphase;
+    rho = (int)blockIdx.z - l * a.nphase;
+    a.x += l * a.ls_x;
+    if (a.skip) a.skip += l * a.ls_skip;
+    if (a.out_raw) a.out_raw += l * a.ls_raw;
+    if (a.out_snake) a.out_snake += l * a.ls_snake;
+    if (a.out_f32) a.out_f32 += l * a.ls_f32;
+  }
+  return a;
+}
 
 __device__ __forceinline__ float snake(float y, float a, float inv_a) {
   // hardware v_sin_f32 (input in revolutions) instead of the libm range-reduced sinf: the epilogue,
@@ -263,7 +284,9 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, const f32x4_t (
 // channels: the wide tile issues each weight tile once per 256 output rows (twice the MFMAs per A piece and
 // per barrier). Every output's K order and MFMA chain are the tile's own, so both give the same bits.
 template <int WM, int WN, int NS, bool HALO, int NWN>
-__global__ __launch_bounds__(128 * NWN) void conv_kernel(const ConvArgs a) {
+__global__ __launch_bounds__(128 * NWN) void conv_kernel(const ConvArgs a0) {
+  int rho;
+  const ConvArgs a = conv_lane_args(a0, rho);
   constexpr int NW = 2 * NWN;
   constexpr int HALO_PIECES = (16 * WN * NWN + HALO_TAPS_ROWS) / 16;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -291,7 +314,6 @@ __global__ __launch_bounds__(128 * NWN) void conv_kernel(const ConvArgs a) {
   constexpr int LDS_BYTES = RING > TILE_BYTES ? RING : TILE_BYTES;
   __shared__ __attribute__((aligned(1024))) char lds_raw[LDS_BYTES];
   const int co_blk = blockIdx.y * BM, q_blk = blockIdx.x * BN;
-  const int rho = blockIdx.z;
   const f16_t* const wts = a.w + (size_t)rho * a.w_phase;
   const int in_off = a.nphase > 1 ? (rho + a.phase_pad) / a.out_stride : a.in_off;
   const int out_phase = a.nphase > 1 ? rho : a.out_phase;
@@ -392,7 +414,9 @@ __global__ __launch_bounds__(128 * NWN) void conv_kernel(const ConvArgs a) {
 // workgroup per CU. K order: (channel step, tap), conv_kernel's halo order, so every output's MFMA chain and
 // bits are the same as conv_kernel's.
 template <int WM, int WN, int TAPS, int CG, int HROWS>
-__global__ __launch_bounds__(512) void conv_stage_kernel(const ConvArgs a) {
+__global__ __launch_bounds__(512) void conv_stage_kernel(const ConvArgs a0) {
+  int rho;
+  const ConvArgs a = conv_lane_args(a0, rho);
   constexpr int NWN = 4, NW = 8;
   constexpr int BM = 32 * WM, BN = 64 * WN, NPA = BM / 16;
   constexpr int HP = (BN + HROWS + 15) / 16;  // halo pieces per channel step (host-checked)
@@ -411,7 +435,6 @@ __global__ __launch_bounds__(512) void conv_stage_kernel(const ConvArgs a) {
 #pragma unroll
     for (int j = 0; j < WN; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   const int co_blk = blockIdx.y * BM, q_blk = blockIdx.x * BN;
-  const int rho = blockIdx.z;
   const f16_t* const wts = a.w + (size_t)rho * a.w_phase;
   const int in_off = a.nphase > 1 ? (rho + a.phase_pad) / a.out_stride : a.in_off;
   const int out_phase = a.nphase > 1 ? rho : a.out_phase;
@@ -504,7 +527,9 @@ __global__ __launch_bounds__(512) void conv_stage_kernel(const ConvArgs a) {
 // back-pressure stalls no MFMA: stage s + 1's pieces are issued right after the barrier that opens stage s and
 // land while its MFMAs run. Same stage buffers, K order and epilogue as conv_stage_kernel (bit-identical).
 template <int WM, int TAPS, int CG, int HROWS>
-__global__ __launch_bounds__(768) void conv_ldr_kernel(const ConvArgs a) {
+__global__ __launch_bounds__(768) void conv_ldr_kernel(const ConvArgs a0) {
+  int rho;
+  const ConvArgs a = conv_lane_args(a0, rho);
   constexpr int NWN = 4, WN = 4, NW = 8, NLD = 4;
   constexpr int BM = 32 * WM, BN = 64 * WN, NPA = BM / 16;
   constexpr int HP = (BN + HROWS + 15) / 16;
@@ -524,7 +549,6 @@ __global__ __launch_bounds__(768) void conv_ldr_kernel(const ConvArgs a) {
 #pragma unroll
     for (int j = 0; j < WN; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   const int co_blk = blockIdx.y * BM, q_blk = blockIdx.x * BN;
-  const int rho = blockIdx.z;
   const f16_t* const wts = a.w + (size_t)rho * a.w_phase;
   const int in_off = a.nphase > 1 ? (rho + a.phase_pad) / a.out_stride : a.in_off;
   const int out_phase = a.nphase > 1 ? rho : a.out_phase;
@@ -603,8 +627,11 @@ __global__ __launch_bounds__(768) void conv_ldr_kernel(const ConvArgs a) {
 
 // quantizer.from_codes (modeling_dac.py:347-371): 9 x [codebook gather (8-d) -> 1x1 conv to 1024 + bias], summed
 __global__ __launch_bounds__(256) void from_codes_kernel(const int64_t* codes, int T, const float* cbooks,
-                                                          const float* pw, const float* pb, f16_t* z) {
+                                                          const float* pw, const float* pb, f16_t* z,
+                                                          size_t ls_codes, size_t ls_z) {
   const int t = blockIdx.x;
+  codes += blockIdx.y * ls_codes;  // blockIdx.y: the lane
+  z += blockIdx.y * ls_z;
   __shared__ float lat[ZMI_NCB][8];
   if (threadIdx.x < ZMI_NCB * 8) {
     const int i = threadIdx.x >> 3, j = threadIdx.x & 7;
@@ -761,22 +788,47 @@ extern "C" int zmi_dac_vq(const float* latents, int t, const float* in_w, const 
   return 0;
 }
 
-extern "C" int zmi_dac_from_codes(const int64_t* codes, int T, const float* codebooks, const float* proj_w,
-                                  const float* proj_b, void* z, void* stream) {
+// lanes > 1: every activation buffer's lane stride covers one lane's extent (0 extent: the buffer is absent)
+static bool lane_stride_ok(int lanes, int64_t stride, size_t extent) {
+  return lanes == 1 || extent == 0 || (stride >= 0 && (uint64_t)stride >= extent);
+}
+
+extern "C" int zmi_dac_from_codes_lanes(const int64_t* codes, int T, const float* codebooks, const float* proj_w,
+                                        const float* proj_b, void* z, int lanes, int64_t ls_codes, int64_t ls_z,
+                                        void* stream) {
+  if (lanes < 1 || lanes > 65535) return zmi_fail_msg("dac_from_codes: 1 <= lanes <= 65535");
   if (T <= 0) return 0;
-  hipLaunchKernelGGL(from_codes_kernel, dim3(T), dim3(256), 0, (hipStream_t)stream, codes, T, codebooks, proj_w,
-                     proj_b, (f16_t*)z);
+  if (!lane_stride_ok(lanes, ls_codes, (size_t)ZMI_NCB * T) || !lane_stride_ok(lanes, ls_z, (size_t)T * 1024))
+    return zmi_fail_msg("dac_from_codes: a lane stride is smaller than a lane's extent");
+  hipLaunchKernelGGL(from_codes_kernel, dim3(T, lanes), dim3(256), 0, (hipStream_t)stream, codes, T, codebooks, proj_w,
+                     proj_b, (f16_t*)z, lanes > 1 ? (size_t)ls_codes : 0, lanes > 1 ? (size_t)ls_z : 0);
   ZMI_CHECK(hipGetLastError());
   return 0;
 }
 
-// Tile height: the largest BM = 32 WM (WM in 4, 3, 2, 1, dividing c_out) whose grid still gives every CU
-// about two workgroups; the early, few-frame stages (conv1 and block 0 at 861 frames: 84-336 workgroups at
-// BM = 128) are latency-bound per workgroup, so more, shorter tiles finish sooner there.
+extern "C" int zmi_dac_from_codes(const int64_t* codes, int T, const float* codebooks, const float* proj_w,
+                                  const float* proj_b, void* z, void* stream) {
+  return zmi_dac_from_codes_lanes(codes, T, codebooks, proj_w, proj_b, z, 1, 0, 0, stream);
+}
+
+// A time tile is cut per lane, so with many short lanes a tall tile can be mostly padding (a 36-row conv1 window
+// fills 14 % of a 256-row tile): with lanes > 1 the bn-row tile is taken only where it pads the lane's n_out rows
+// at most slack8 / 8 more than the smallest, 128-row tile does (1/8 for the 512-row staged tile and conv_kernel's
+// 256-row tile, whose gain over the next smaller one is a fraction; 1/2 for the 256-row staged tile, whose
+// alternative is conv_kernel). One lane: always (the single-utterance choice is unchanged).
+static bool lane_tile_ok(const ConvArgs& a, int bn, int slack8) {
+  if (a.lanes == 1) return true;
+  const long full = ((long)a.n_out + bn - 1) / bn * bn, least = ((long)a.n_out + 127) / 128 * 128;
+  return full * 8 <= least * (8 + slack8);
+}
+
+// Tile height: the largest BM = 32 WM (WM in 4, 3, 2, 1, dividing c_out) whose grid (all lanes' workgroups) still
+// gives every CU about two workgroups; the early, few-frame stages (conv1 and block 0 at 861 frames: 84-336
+// workgroups at BM = 128) are latency-bound per workgroup, so more, shorter tiles finish sooner there.
 template <int NWN>
 static int launch_conv_t(const ConvArgs& a, hipStream_t s) {
   constexpr int WN = 4, BN = 16 * WN * NWN, NT = 128 * NWN;
-  const unsigned nq = (unsigned)((a.n_out + BN - 1) / BN), nz = (unsigned)a.nphase;
+  const unsigned nq = (unsigned)((a.n_out + BN - 1) / BN), nz = (unsigned)(a.nphase * a.lanes);
   const int want = 256 / (NWN / 2);
   int wm = 0;
   for (int c : {4, 3, 2, 1})
@@ -832,7 +884,7 @@ static int launch_stage(const ConvArgs& a, hipStream_t s) {
   // A grid with too few 512-row tiles (conv1 at 861 frames: 96) takes the 256-row tiles before conv_kernel (its 192
   // workgroups: 40 us against 136 on conv_kernel).
   const long min_wg = zmi_option(ZMI_OPT_DAC_STAGE_MIN);
-  const unsigned nz = (unsigned)a.nphase;
+  const unsigned nz = (unsigned)(a.nphase * a.lanes);
   auto pick = [&](int bn, int wm_max, unsigned* nq_out) {  // the largest tile height whose grid reaches min_wg
     const unsigned nq = (unsigned)((a.n_out + bn - 1) / bn);
     int w = 0;
@@ -845,11 +897,11 @@ static int launch_stage(const ConvArgs& a, hipStream_t s) {
     return w && (long)nq * nz * (a.c_out / (32 * w)) >= min_wg ? w : 0;
   };
   unsigned nq = 0;
-  bool wide = cls == 0 && (mask & 8);
+  bool wide = cls == 0 && (mask & 8) && lane_tile_ok(a, 512, 1);
   int wm = wide ? pick(512, 3, &nq) : 0;
   if (!wm) {
     wide = false;
-    wm = pick(256, 4, &nq);
+    wm = lane_tile_ok(a, 256, 4) ? pick(256, 4, &nq) : 0;
   }
   if (!wm) return 1;
   if (cls == 1 && cg == 3 && wm < 3) return 1;  // instantiated for the 96-channel stages only
@@ -908,27 +960,60 @@ static int launch_conv(const ConvArgs& a, hipStream_t s) {
   const int st = launch_stage(a, s);
   if (st != 1) return st;
   const int wide = zmi_option(ZMI_OPT_DAC_WIDE);
-  if (wide == 2 || (wide == 1 && (long)a.n_out * a.nphase * (a.c_out / 32) >= (long)zmi_option(ZMI_OPT_DAC_WIDE_MIN) * 256))
+  if (wide == 2 || (wide == 1 && lane_tile_ok(a, 256, 1) &&
+                    (long)a.n_out * a.nphase * a.lanes * (a.c_out / 32) >= (long)zmi_option(ZMI_OPT_DAC_WIDE_MIN) * 256))
     return launch_conv_t<4>(a, s);
   return launch_conv_t<2>(a, s);
+}
+
+// the lane arguments of a launch: lanes and every present buffer's stride checked against one lane's extent
+static int set_lanes(ConvArgs& a, int lanes, int64_t ls_x, int64_t ls_skip, int64_t ls_raw, int64_t ls_snake,
+                     int64_t ls_f32) {
+  if (lanes < 1) return zmi_fail_msg("dac_conv: lanes >= 1");
+  if ((long)lanes * a.nphase > 65535) return zmi_fail_msg("dac_conv: lanes * phases > 65535 (grid z)");
+  if (lanes == 1) return 0;
+  const size_t xe = (size_t)a.t_in * a.c_in, oe = (size_t)a.t_out * a.c_out;
+  if (!lane_stride_ok(lanes, ls_x, xe) || !lane_stride_ok(lanes, ls_skip, a.skip ? oe : 0) ||
+      !lane_stride_ok(lanes, ls_raw, a.out_raw ? oe : 0) || !lane_stride_ok(lanes, ls_snake, a.out_snake ? oe : 0) ||
+      !lane_stride_ok(lanes, ls_f32, a.out_f32 ? (a.tanh_c0 ? (size_t)a.t_out : oe) : 0))
+    return zmi_fail_msg("dac_conv: a lane stride is smaller than a lane's extent");
+  a.lanes = lanes;
+  a.ls_x = (size_t)ls_x;
+  a.ls_skip = a.skip ? (size_t)ls_skip : 0;
+  a.ls_raw = a.out_raw ? (size_t)ls_raw : 0;
+  a.ls_snake = a.out_snake ? (size_t)ls_snake : 0;
+  a.ls_f32 = a.out_f32 ? (size_t)ls_f32 : 0;
+  return 0;
+}
+
+extern "C" int zmi_dac_conv_lanes(const void* x, int t_in, int c_in, const void* w, const float* bias, int c_out,
+                                  int taps, int tap_step, int in_off, int n_out, int out_stride, int out_phase,
+                                  int t_out, const void* skip, void* out_raw, void* out_snake, const float* alpha,
+                                  float* out_f32, int lanes, int64_t ls_x, int64_t ls_skip, int64_t ls_raw,
+                                  int64_t ls_snake, int64_t ls_f32, void* stream) {
+  if (c_in % 32) return zmi_fail_msg("dac_conv: c_in % 32");
+  if (lanes < 1) return zmi_fail_msg("dac_conv: lanes >= 1");
+  if (n_out <= 0) return 0;
+  if ((size_t)(n_out - 1) * out_stride + out_phase >= (size_t)t_out) return zmi_fail_msg("dac_conv: output bounds");
+  ConvArgs a{(const f16_t*)x, t_in, c_in, (const f16_t*)w, bias, c_out, taps, tap_step, in_off, n_out,
+             out_stride, out_phase, t_out, (const f16_t*)skip, (f16_t*)out_raw, (f16_t*)out_snake, alpha, out_f32, 0, 1, 0, 0};
+  int rc = set_lanes(a, lanes, ls_x, ls_skip, ls_raw, ls_snake, ls_f32);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  // 128-step time tiles: 64- and 32-step tiles measured 15 % and 65 % slower (more workgroups do
+  // not hide the per-K-step load latency; DESIGN.md §4)
+  rc = launch_conv(a, s);
+  if (rc) return rc;
+  ZMI_CHECK(hipGetLastError());
+  return 0;
 }
 
 extern "C" int zmi_dac_conv(const void* x, int t_in, int c_in, const void* w, const float* bias, int c_out, int taps,
                             int tap_step, int in_off, int n_out, int out_stride, int out_phase, int t_out,
                             const void* skip, void* out_raw, void* out_snake, const float* alpha, float* out_f32,
                             void* stream) {
-  if (c_in % 32) return zmi_fail_msg("dac_conv: c_in % 32");
-  if (n_out <= 0) return 0;
-  if ((size_t)(n_out - 1) * out_stride + out_phase >= (size_t)t_out) return zmi_fail_msg("dac_conv: output bounds");
-  ConvArgs a{(const f16_t*)x, t_in, c_in, (const f16_t*)w, bias, c_out, taps, tap_step, in_off, n_out,
-             out_stride, out_phase, t_out, (const f16_t*)skip, (f16_t*)out_raw, (f16_t*)out_snake, alpha, out_f32, 0, 1, 0, 0};
-  hipStream_t s = (hipStream_t)stream;
-  // 128-step time tiles: 64- and 32-step tiles measured 15 % and 65 % slower (more workgroups do
-  // not hide the per-K-step load latency; DESIGN.md §4)
-  const int rc = launch_conv(a, s);
-  if (rc) return rc;
-  ZMI_CHECK(hipGetLastError());
-  return 0;
+  return zmi_dac_conv_lanes(x, t_in, c_in, w, bias, c_out, taps, tap_step, in_off, n_out, out_stride, out_phase, t_out,
+                            skip, out_raw, out_snake, alpha, out_f32, 1, 0, 0, 0, 0, 0, stream);
 }
 
 extern "C" int zmi_dac_conv_out(const void* x, int t, int c_in, const void* w_pad, const float* bias_pad, float* out,
@@ -945,17 +1030,48 @@ extern "C" int zmi_dac_conv_out(const void* x, int t, int c_in, const void* w_pa
   return 0;
 }
 
-extern "C" int zmi_dac_conv_out_range(const void* x, int t, int c_in, const void* w_pad, const float* bias_pad, int q0,
-                                      int n, float* out, void* stream) {
+extern "C" int zmi_dac_conv_out_range_lanes(const void* x, int t, int c_in, const void* w_pad, const float* bias_pad,
+                                            int q0, int n, float* out, int lanes, int64_t ls_x, int64_t ls_out,
+                                            void* stream) {
   // zmi_dac_conv_out for samples q0 .. q0 + n - 1 only, written to out[0 .. n): the conv's input offset moves by q0,
   // so each sample has the K order (channel step, tap) and the MFMA chain it has in the whole-length launch (the
   // streaming decoder's crop: a window's halo samples are never computed by the last, longest stage)
   if (c_in % 32) return zmi_fail_msg("dac_conv_out_range: c_in % 32");
   if (q0 < 0 || n < 0 || (long)q0 + n > t) return zmi_fail_msg("dac_conv_out_range: bounds");
+  if (lanes < 1) return zmi_fail_msg("dac_conv_out_range: lanes >= 1");
   if (n == 0) return 0;
   ConvArgs a{(const f16_t*)x, t, c_in, (const f16_t*)w_pad, bias_pad, 32, 7, 1, q0 - 3, n, 1, 0, n,
              nullptr, nullptr, nullptr, nullptr, out, 1, 1, 0, 0};
-  const int rc = launch_conv(a, (hipStream_t)stream);
+  int rc = set_lanes(a, lanes, ls_x, 0, 0, 0, ls_out);
+  if (rc) return rc;
+  rc = launch_conv(a, (hipStream_t)stream);
+  if (rc) return rc;
+  ZMI_CHECK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int zmi_dac_conv_out_range(const void* x, int t, int c_in, const void* w_pad, const float* bias_pad, int q0,
+                                      int n, float* out, void* stream) {
+  return zmi_dac_conv_out_range_lanes(x, t, c_in, w_pad, bias_pad, q0, n, out, 1, 0, 0, stream);
+}
+
+extern "C" int zmi_dac_conv_t_lanes(const void* x, int t_in, int c_in, const void* w_phases, const float* bias,
+                                    int c_out, int stride, int pad, void* out_raw, void* out_snake, const float* alpha,
+                                    int lanes, int64_t ls_x, int64_t ls_raw, int64_t ls_snake, void* stream) {
+  // ConvTranspose1d(c_in, c_out, k = 2 stride, stride, padding = pad) (modeling_dac.py:222-240) in polyphase
+  // form, all phases in one launch: out[stride q + rho] = bias + W_rho[0] x[q + c] + W_rho[1] x[q + c - 1],
+  // c = (rho + pad) / stride; w_phases fp16 [stride][2][c_in / 32][c_out][32] (W_rho[j] = w[:, :, (rho + pad) % stride
+  // + j stride]^T); output length stride * t_in
+  if (c_in % 32) return zmi_fail_msg("dac_conv_t: c_in % 32");
+  if (lanes < 1) return zmi_fail_msg("dac_conv_t: lanes >= 1");
+  if (t_in <= 0) return 0;
+  if (stride < 1 || pad < 0) return zmi_fail_msg("dac_conv_t: stride >= 1, pad >= 0");
+  ConvArgs a{(const f16_t*)x, t_in, c_in, (const f16_t*)w_phases, bias, c_out, 2, -1, 0, t_in, stride, 0,
+             stride * t_in, nullptr, (f16_t*)out_raw, (f16_t*)out_snake, alpha, nullptr, 0, stride, pad,
+             (size_t)2 * c_out * c_in};
+  int rc = set_lanes(a, lanes, ls_x, 0, ls_raw, ls_snake, 0);
+  if (rc) return rc;
+  rc = launch_conv(a, (hipStream_t)stream);
   if (rc) return rc;
   ZMI_CHECK(hipGetLastError());
   return 0;
@@ -963,18 +1079,6 @@ extern "C" int zmi_dac_conv_out_range(const void* x, int t, int c_in, const void
 
 extern "C" int zmi_dac_conv_t(const void* x, int t_in, int c_in, const void* w_phases, const float* bias, int c_out,
                               int stride, int pad, void* out_raw, void* out_snake, const float* alpha, void* stream) {
-  // ConvTranspose1d(c_in, c_out, k = 2 stride, stride, padding = pad) (modeling_dac.py:222-240) in polyphase
-  // form, all phases in one launch: out[stride q + rho] = bias + W_rho[0] x[q + c] + W_rho[1] x[q + c - 1],
-  // c = (rho + pad) / stride; w_phases fp16 [stride][2][c_in / 32][c_out][32] (W_rho[j] = w[:, :, (rho + pad) % stride
-  // + j stride]^T); output length stride * t_in
-  if (c_in % 32) return zmi_fail_msg("dac_conv_t: c_in % 32");
-  if (t_in <= 0) return 0;
-  if (stride < 1 || pad < 0) return zmi_fail_msg("dac_conv_t: stride >= 1, pad >= 0");
-  ConvArgs a{(const f16_t*)x, t_in, c_in, (const f16_t*)w_phases, bias, c_out, 2, -1, 0, t_in, stride, 0,
-             stride * t_in, nullptr, (f16_t*)out_raw, (f16_t*)out_snake, alpha, nullptr, 0, stride, pad,
-             (size_t)2 * c_out * c_in};
-  const int rc = launch_conv(a, (hipStream_t)stream);
-  if (rc) return rc;
-  ZMI_CHECK(hipGetLastError());
-  return 0;
+  return zmi_dac_conv_t_lanes(x, t_in, c_in, w_phases, bias, c_out, stride, pad, out_raw, out_snake, alpha, 1, 0, 0, 0,
+                              stream);
 }

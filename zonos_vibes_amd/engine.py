@@ -798,6 +798,22 @@ class HipEngine:
             ev.record(self.stream)
         return ev
 
+    def snapshot_all_ints(self) -> int:
+        return len(ST_FIELDS) * self.st_all.shape[1] + 3
+
+    def snapshot_all(self, host: torch.Tensor) -> torch.cuda.Event:
+        """snapshot() of every slot: the whole state table (ST_FIELDS x slots, field-major: field j of slot s at
+        j * slots + s) as one device-to-host copy, then the three error words, into `host` (pinned int32
+        [snapshot_all_ints()]), asynchronously on the engine's stream; the returned event marks their completion."""
+        n = self.st_all.numel()
+        with torch.cuda.stream(self.stream):
+            host[:n].copy_(self.st_all.view(-1), non_blocking=True)
+            host[n: n + 1].copy_(self.attn_work[:4].view(torch.int32), non_blocking=True)
+            host[n + 1: n + 3].copy_(self.blk_err[:2], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(self.stream)
+        return ev
+
     def read_final_codes(self, slot: int, t0: int, t1: int) -> torch.Tensor:
         """Frames t0 .. t1 - 1 of read_codes' result -> [1, 9, t1 - t0] int64, enqueued on the engine's stream with no
         host sync: the caller orders its consumer after the stream (an event) and reads only frames that are final

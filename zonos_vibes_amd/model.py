@@ -4,6 +4,7 @@
     codes = model.generate(prefix_conditioning)                          # [1, 9, T] int64
     wav = model.autoencoder.decode(codes)                                # [1, 1, 512 T] fp32
     for wav in model.stream(prefix_conditioning): ...                    # the same samples, in chunks, as they are ready
+    for i, wav, last in model.stream_batch(conds): ...                   # many utterances' chunks, each as decode(generate_batch)
 
 `generate` keeps the reference's arguments and batch_size=1 semantics; `generate_batch`
 runs many independent utterances through the slots of one engine (continuous batching at
@@ -44,6 +45,7 @@ class Zonos:
         self.spk_clone_model = None      # created lazily (model.py:90-93) by make_speaker_embedding
         self._spk_synthetic_seed = None  # Zonos.synthetic: the seed of the synthetic speaker encoder
         self._stream_decoders: dict = {}  # stream(): one DACStreamDecoder per chunk_frames
+        self._stream_batch_decoders: dict = {}  # stream_batch(): one DACBatchStreamDecoder per chunk_frames
         # stream(): True lets the DAC windows run beside the next decode steps. Measured: the decode
         # step's codes are then not reproducible (a few utterances in ten diverge from generate() at some frame), so
         # the windows run between the rounds of steps instead and stream() is exact. tools/bench_stream.py sets it to
@@ -339,6 +341,119 @@ class Zonos:
                         e.pos_hi[s] = 0  # its rows are inactive (position -1): no bound on the attention form
             fill()
         return results
+
+    @torch.inference_mode()
+    def stream_batch(self, conds: Sequence[torch.Tensor], prefixes: Sequence[torch.Tensor | None] | None = None,
+                     max_new_tokens: Sequence[int] | int = 86 * 30, cfg_scale: float = 2.0,
+                     sampling_params: dict = dict(min_p=0.1), seeds: Sequence[int] | None = None,
+                     max_slots: int | None = None, chunk_frames: int = 16):
+        """generate_batch() + autoencoder.decode() per utterance as a generator of (utterance index, waveform chunk
+        [1, 1, 512 n] fp32 (device), last): every utterance's audio is yielded while it and the others are still being
+        generated. With the same seeds, utterance i's chunks concatenated are bit for bit
+        autoencoder.decode(generate_batch(...)[i]); each utterance yields exactly one item with last = True (its chunk
+        may be empty).
+
+        A round is `chunk_frames` decode steps over slots 0 .. the highest busy one (generate_batch's sizes and
+        batch_shrink rule), one copy of every slot's state to the host, the read of the frames the round made final
+        in every busy slot, and ONE push of all of them to a DACBatchStreamDecoder, which decodes the slots' windows
+        of equal shape as lanes of one launch sequence. Slots that ended are flushed and refilled from the queue
+        (longest first). The DAC windows run between the rounds, never beside decode steps (stream()'s ordering rule,
+        DESIGN.md §5g): they are ordered behind the round's reads and the next round's steps wait for the
+        autoencoder's stream. The state is read before the push, so nothing is decoded past an utterance's end."""
+        assert cfg_scale != 1, "TODO: add support for cfg_scale=1"
+        if chunk_frames < 1:
+            raise ValueError("chunk_frames >= 1")
+        n = len(conds)
+        if n == 0:
+            return
+        prefixes = list(prefixes) if prefixes is not None else [None] * n
+        mnt = [max_new_tokens] * n if isinstance(max_new_tokens, int) else list(max_new_tokens)
+        seeds = list(seeds) if seeds is not None else [_draw_seed() for _ in range(n)]
+        plen = [0 if p is None else p.shape[2] for p in prefixes]
+        need_seq = max(c.shape[1] + p + m + 9 for c, p, m in zip(conds, plen, mnt))
+        need_pre = max(c.shape[1] + p + 1 for c, p in zip(conds, plen))
+        slots = min(max_slots or n, n)
+        self._ensure_capacity(slots, need_seq, need_pre)
+        e, ae = self.engine, self.autoencoder
+        key = (id(ae), int(chunk_frames))
+        dec = self._stream_batch_decoders.get(key)
+        if dec is None or dec.lanes < slots:  # kept: its graphs and stage buffers serve every later call
+            dec = self._stream_batch_decoders[key] = ae.stream_decoder_batch(slots, chunk_frames)
+        for s in range(slots):
+            dec.reset(s)  # (an earlier stream_batch closed before its end)
+        queue = sorted(range(n), key=lambda i: -mnt[i])  # longest-processing-time first, so the tail is short
+        owner = [-1] * slots
+        remaining, steps, read_to = [0] * slots, [0] * slots, [0] * slots
+        sizes = sorted({slots} | {b for b in (1, 2, 4, 8, 16, 24, 32, 40, 48, 56) if b < slots})
+        nf, S = len(ST_FIELDS), e.st_all.shape[1]
+        host = torch.empty(e.snapshot_all_ints(), dtype=torch.int32).pin_memory()
+        cur = torch.cuda.current_stream(self._device)
+
+        def fill():
+            items = []
+            for s in range(slots):
+                if owner[s] < 0 and queue:
+                    i = queue.pop(0)
+                    params = SamplingParams.from_dict(dict(sampling_params), cfg_scale, seeds[i])
+                    items.append((s, conds[i], prefixes[i], mnt[i], params))
+                    owner[s] = i
+                    remaining[s], steps[s], read_to[s] = mnt[i] + 8, 0, 0
+            e.prefill_many(items)
+
+        try:
+            fill()
+            while any(o >= 0 for o in owner):
+                k = min(chunk_frames, max(r for s, r in enumerate(remaining) if owner[s] >= 0))
+                hi = max(s for s in range(slots) if owner[s] >= 0) + 1 if e.batch_shrink else slots
+                e.stream.wait_stream(ae.stream)  # the previous round's windows first
+                e.step(k, slots=next(b for b in sizes if b >= hi))
+                e.snapshot_all(host).synchronize()
+                vals = host.tolist()
+                if any(vals[nf * S:]):  # the words check_errors() reads, copied with the state
+                    e.check_errors()
+                pieces, ended = {}, []
+                for s in range(slots):
+                    if owner[s] < 0:
+                        continue
+                    i = owner[s]
+                    remaining[s] -= k
+                    steps[s] += k
+                    stt = {f: vals[j * S + s] for j, f in enumerate(ST_FIELDS)}
+                    if stt["active"]:
+                        t1 = min(plen[i] + 1 + steps[s] - 9, plen[i] + mnt[i])
+                        if t1 > read_to[s] and stt["offset"] - 9 < t1:
+                            raise RuntimeError("stream_batch: a slot's offset is behind the steps enqueued")
+                    else:  # ended (EOS countdown or max_new_tokens): read_codes' count
+                        t1 = codes_count(stt)
+                        ended.append(s)
+                    t1 = max(t1, read_to[s])
+                    if t1 > read_to[s]:
+                        pieces[s] = e.read_final_codes(s, read_to[s], t1)
+                        read_to[s] = t1
+                with torch.cuda.stream(e.stream):  # ordered behind the reads; the next round waits for ae.stream
+                    wavs = dec.push(pieces) if pieces else {}
+                    tails = dec.flush(ended) if ended else {}
+                    for s, tail in tails.items():
+                        w = wavs.get(s)
+                        wavs[s] = tail if w is None or w.shape[-1] == 0 else \
+                            w if tail.shape[-1] == 0 else torch.cat([w, tail], dim=-1)
+                cur.wait_stream(e.stream)
+                out = []
+                for s in sorted(wavs):
+                    last = s in tails
+                    if wavs[s].shape[-1] or last:
+                        wavs[s].record_stream(cur)
+                        out.append((owner[s], wavs[s], last))
+                for s in ended:
+                    owner[s] = -1
+                    e.pos_hi[s] = 0  # its rows are inactive (position -1): no bound on the attention form
+                fill()  # before the round's audio is handed out: the consumer's time is not the engine's
+                yield from out
+        finally:
+            for s in range(slots):
+                dec.reset(s)
+                if owner[s] >= 0:
+                    e.release(s)
 
     def __repr__(self):
         bb = self.config.backbone

@@ -95,25 +95,31 @@ class DACStreamDecoder:
             a = b
         return out
 
-    def _run(self, upto: int) -> torch.Tensor:
-        parts = []
-        for lo, hi, a, b in self._windows(upto, self._recv):
-            w = self._held[:, lo - self._base: hi - self._base]
-            parts.append(self.decode_window(w, a - lo, b - lo))
+    def _plan(self, upto: int):
+        """The decode_window arguments (codes [9, W], f0, f1) that emit frames _emit .. upto - 1."""
+        return [(self._held[:, lo - self._base: hi - self._base], a - lo, b - lo)
+                for lo, hi, a, b in self._windows(upto, self._recv)]
+
+    def _advance(self, upto: int):
         if upto > self._emit:
             self._emit = upto
             keep = max(self._emit - self.R, 0)  # the next window's left halo
             if keep > self._base:
                 self._held = self._held[:, keep - self._base:]
                 self._base = keep
+
+    def _join(self, parts) -> torch.Tensor:
         if not parts:
             return torch.empty(1, 1, 0, dtype=torch.float32, device=self.device)
         return parts[0] if len(parts) == 1 else torch.cat(parts, dim=-1)
 
-    @torch.inference_mode()
-    def push(self, codes: torch.Tensor) -> torch.Tensor:
-        """codes [1, 9, n] or [9, n] int64 (n >= 0) -> [1, 1, 512 m] fp32: the m frames whose right lookahead is now
-        available (m may be 0)."""
+    def _run(self, upto: int) -> torch.Tensor:
+        parts = [self.decode_window(w, f0, f1) for w, f0, f1 in self._plan(upto)]
+        self._advance(upto)
+        return self._join(parts)
+
+    def _take(self, codes: torch.Tensor) -> int:
+        """Append pushed codes; returns the frame up to which samples can now be emitted."""
         if codes.dim() == 3:
             if codes.shape[0] != 1:
                 raise ValueError("DACStreamDecoder decodes one utterance: codes [1, 9, n] or [9, n]")
@@ -124,7 +130,13 @@ class DACStreamDecoder:
             codes = codes.to(self.device, torch.int64)
             self._held = codes if self._held is None or self._held.shape[1] == 0 else torch.cat([self._held, codes], 1)
             self._recv += codes.shape[1]
-        return self._run(max(self._recv - self.R, self._emit))
+        return max(self._recv - self.R, self._emit)
+
+    @torch.inference_mode()
+    def push(self, codes: torch.Tensor) -> torch.Tensor:
+        """codes [1, 9, n] or [9, n] int64 (n >= 0) -> [1, 1, 512 m] fp32: the m frames whose right lookahead is now
+        available (m may be 0)."""
+        return self._run(self._take(codes))
 
     @torch.inference_mode()
     def flush(self) -> torch.Tensor:
@@ -134,4 +146,74 @@ class DACStreamDecoder:
         return out
 
 
-__all__ = ["dac_lookahead_frames", "DAC_LOOKAHEAD_FRAMES", "DACStreamDecoder", "DAC_HOP"]
+class DACBatchStreamDecoder:
+    """`lanes` independent DACStreamDecoders whose windows are decoded together: every lane keeps a DACStreamDecoder's
+    held / base / recv / emit state and its `_windows` rule, and all the windows one push() or flush() call makes
+    due, over all its lanes, go to ONE call of
+
+        decode_windows(list of (codes [9, W] int64, f0, f1)) -> list of [1, 1, 512 (f1 - f0)] fp32
+
+    so the GPU side can decode windows of equal shape in one launch sequence (DACAutoencoder.stream_decoder_batch).
+    Per lane, the concatenated returns are exactly what a DACStreamDecoder of its own returns for the same pushes.
+    """
+
+    def __init__(self, decode_windows: Callable[[list], list], lanes: int, chunk_frames: int = 16,
+                 lookahead: int = DAC_LOOKAHEAD_FRAMES, device=None):
+        if lanes < 1:
+            raise ValueError("lanes >= 1")
+        self.decode_windows = decode_windows
+        self._lanes = [DACStreamDecoder(None, chunk_frames, lookahead, device) for _ in range(int(lanes))]
+        self.chunk, self.R, self.device = self._lanes[0].chunk, self._lanes[0].R, self._lanes[0].device
+
+    @property
+    def lanes(self) -> int:
+        return len(self._lanes)
+
+    def frames_received(self, lane: int) -> int:
+        return self._lanes[lane].frames_received
+
+    def frames_emitted(self, lane: int) -> int:
+        return self._lanes[lane].frames_emitted
+
+    def _run(self, upto: dict) -> dict:
+        """upto {lane: frame}: emit every lane's frames up to its frame, all windows in one decode_windows call."""
+        plans = {lane: self._lanes[lane]._plan(u) for lane, u in upto.items()}
+        flat = [w for lane in plans for w in plans[lane]]
+        wavs = list(self.decode_windows(flat)) if flat else []
+        if len(wavs) != len(flat):
+            raise RuntimeError(f"decode_windows returned {len(wavs)} waveforms for {len(flat)} windows")
+        out, i = {}, 0
+        for lane, plan in plans.items():
+            dec = self._lanes[lane]
+            dec._advance(upto[lane])
+            out[lane] = dec._join(wavs[i: i + len(plan)])
+            i += len(plan)
+        return out
+
+    @torch.inference_mode()
+    def push(self, codes: dict) -> dict:
+        """{lane: codes [9, n] or [1, 9, n] int64} -> {lane: [1, 1, 512 m] fp32}: per lane, the m frames whose right
+        lookahead is now available (m may be 0)."""
+        for lane, c in codes.items():  # every lane's arguments are checked before any lane's state changes
+            if not 0 <= lane < len(self._lanes):
+                raise ValueError(f"lane {lane} outside [0, {len(self._lanes)})")
+            if c.dim() not in (2, 3) or c.shape[-2] != N_CODEBOOKS or (c.dim() == 3 and c.shape[0] != 1):
+                raise ValueError(f"codes must be [1, {N_CODEBOOKS}, n] or [{N_CODEBOOKS}, n]")
+        return self._run({lane: self._lanes[lane]._take(c) for lane, c in codes.items()})
+
+    @torch.inference_mode()
+    def flush(self, lanes) -> dict:
+        """These lanes' utterances have ended: {lane: the samples of its frames not yet emitted}. The lanes are then
+        ready for new utterances."""
+        lanes = list(lanes)
+        out = self._run({lane: self._lanes[lane]._recv for lane in lanes})
+        for lane in lanes:
+            self._lanes[lane]._reset()
+        return out
+
+    def reset(self, lane: int):
+        """Drop a lane's utterance without decoding what is left of it."""
+        self._lanes[lane]._reset()
+
+
+__all__ = ["dac_lookahead_frames", "DAC_LOOKAHEAD_FRAMES", "DACStreamDecoder", "DACBatchStreamDecoder", "DAC_HOP"]
