@@ -44,9 +44,18 @@ enum { ZMI_PACK_IDENTITY = 0, ZMI_PACK_SWIGLU = 1 };
  *   GRMS   mamba-ssm RMSNormGated(X, z) * ln_w (norm_before_gate=False, one group), aux = the f32 gate
  *          z * sigmoid(z) (zmi_mamba2_step's gz), at most 4 rows. */
 enum { ZMI_PRO_AUTO = 0, ZMI_PRO_ADDLN = 2, ZMI_PRO_GRMS = 3, ZMI_PRO_GRMS_G = 4 };
+/* weight format (ZmiGemvArgs.w_fmt):
+ *   BF16  bf16 weights in layout M8 (zmi_pack_weight);
+ *   FP8   weight-only 8-bit: W[n][k] = 2^w_exp[n] * q[n][k], q OCP float8_e4m3fn (never NaN), one signed exponent per
+ *         packed column; layout M8F8 (zonos_vibes_amd/quant.py pack_m8f8): the bytes of the M8 chunks 2p and 2p + 1 of
+ *         a column group share one 1 KiB piece, lane l holding its 8 weights of chunk 2p then its 8 of chunk 2p + 1.
+ *         Every 2^w_exp q is a bf16 value, and zmi_gemv_launch returns the bits of the BF16 launch on those dequantised
+ *         weights. Built for the plain / LayerNorm prologue, K in {512, 1024, 2048, 8192} and the SWIGLU, RESIDUAL and
+ *         F32 epilogues (the MLP projections); zmi_gemv_launch only: the split-K GEMM and the fused blocks refuse it. */
+enum { ZMI_WFMT_BF16 = 0, ZMI_WFMT_FP8 = 1 };
 
 typedef struct ZmiGemvArgs {
-  const void* W;        /* packed weight (zmi_pack_weight, layout M8)                          */
+  const void* W;        /* packed weight (zmi_pack_weight, layout M8; w_fmt FP8: layout M8F8)   */
   const void* X;        /* bf16 [M][ldx] activations                                          */
   int M, N, K, ldx;     /* N = packed (padded) columns, multiple of 8; K in {512 .. 8192}, pow2  */
   int groups;           /* 8-column groups per workgroup: 0 = library choice, else 1 or 2      */
@@ -68,6 +77,9 @@ typedef struct ZmiGemvArgs {
   int ld_aux;           /* row stride of aux and res_out (elements)                             */
   const void* aux;      /* ADDLN: bf16 residual rows; GRMS: f32 gate rows z * sigmoid(z); GRMS_G: f32 rows g = y * gate (X unused) */
   void* res_out;        /* ADDLN: bf16 [M][ld_aux] new residual, or NULL                         */
+  int w_fmt;            /* ZMI_WFMT_*: 0 = bf16 (layout M8), 1 = E4M3 bytes (layout M8F8) with w_exp */
+  int reserved2;
+  const void* w_exp;    /* FP8: int8 [N] power-of-two exponent of each packed column              */
 } ZmiGemvArgs;
 
 int zmi_pack_weight(const void* src, void* dst, int n_src, int k, int n_pad, int mode, void* stream);

@@ -32,6 +32,7 @@ OPT_SPLITK_STAGE = 17
 ATTNBLK_SELF, ATTNBLK_SPLIT = 256, 512  # zmi_attn_block slices flags: self-scoring / chunk-split forms
 PACK_IDENTITY, PACK_SWIGLU = 0, 1
 PRO_AUTO, PRO_ADDLN, PRO_GRMS, PRO_GRMS_G = 0, 2, 3, 4
+WFMT_BF16, WFMT_FP8 = 0, 1  # GemvArgs.w_fmt: bf16 (layout M8) / E4M3 bytes + per-column exponents (quant.py)
 
 
 class GemvArgs(ctypes.Structure):
@@ -46,6 +47,7 @@ class GemvArgs(ctypes.Structure):
         ("smax", c_int), ("hq", c_int), ("hkv", c_int), ("hd", c_int),
         ("rope", c_void_p), ("diag", c_void_p),
         ("pro", c_int), ("ld_aux", c_int), ("aux", c_void_p), ("res_out", c_void_p),
+        ("w_fmt", c_int), ("reserved2", c_int), ("w_exp", c_void_p),
     ]
 
 
@@ -187,7 +189,7 @@ _SIGS = {
 
 EXPORTED = sorted(_SIGS)
 _lib = None
-ABI_VERSION = 7  # zmi_version() of the library this binding (and its weight packers) is written for
+ABI_VERSION = 8  # zmi_version() of the library this binding (and its weight packers) is written for
 
 
 def load(path: str = LIB_PATH) -> ctypes.CDLL:

@@ -1213,6 +1213,8 @@ int attn_block(const ZmiGemvArgs* qkv, const ZmiGemvArgs* oproj, void* gran, uns
                int slices, const ZmiPrefetch* prefetch, void* stream) {
   const ZmiGemvArgs& a = *qkv;
   if (a.K != 2048 || !a.ln_w) return zmi_fail_msg("attn_block: the QKV projection must be LayerNorm'd with K = 2048");
+  if (a.w_fmt != ZMI_WFMT_BF16 || (oproj && oproj->w_fmt != ZMI_WFMT_BF16))
+    return zmi_fail_msg("attn_block: bf16 weights only");
   const bool addln = a.pro == ZMI_PRO_ADDLN;
   if (a.pro != ZMI_PRO_AUTO && !addln) return zmi_fail_msg("attn_block: prologue must be LayerNorm or ADDLN");
   if (addln && (!a.ln_b || !a.aux || a.ld_aux % 8 || a.res_out == a.aux))

@@ -249,6 +249,8 @@ int launch_splitk(const ZmiGemvArgs& a, int epi, float* part, const void* ln_w, 
 extern "C" int zmi_gemv_splitk_ln(const ZmiGemvArgs* args, int epi, float* part, int64_t part_floats, const void* ln_w,
                                   const void* ln_b, float eps, void* xn, int ldxn, void* stream) {
   const ZmiGemvArgs& a = *args;
+  // before any launch: the kernel would read E4M3 bytes as bf16
+  if (a.w_fmt != ZMI_WFMT_BF16) return zmi_fail_msg("gemv_splitk: bf16 weights only (fp8 weights run zmi_gemv_launch)");
   if (ln_w && (!ln_b || !xn || a.N != 2048 || ldxn < 2048 || ldxn % 8 || a.ldo % 8))
     return zmi_fail_msg("gemv_splitk_ln: the fused LayerNorm needs N = 2048, ln_b, xn (ldxn % 8) and ldo % 8");
   if (epi != ZMI_EPI_RESIDUAL && epi != ZMI_EPI_STORE) return zmi_fail_msg("gemv_splitk: EPI_RESIDUAL or EPI_STORE only");

@@ -61,6 +61,12 @@ extern "C" int zmi_gemv_launch(const ZmiGemvArgs* args, int epi, void* stream) {
     return zmi_fail_msg("gemv: GRMS needs ln_w (the norm weight), aux = the f32 gate or g rows (ld_aux % 8 == 0), M <= 4");
   if (epi == ZMI_EPI_QKV && (a.hd % 8 || a.smax <= 0 || !a.row_pos || !a.row_kv || !a.rope))
     return zmi_fail_msg("gemv: the QKV epilogue needs row_pos, row_kv, rope, smax and hd % 8 == 0");
+  if (a.w_fmt != ZMI_WFMT_BF16 && a.w_fmt != ZMI_WFMT_FP8) return zmi_fail_msg("gemv: unknown weight format");
+  if (a.w_fmt == ZMI_WFMT_FP8 &&
+      (!a.w_exp || ((size_t)a.w_exp & 7) || a.pro != ZMI_PRO_AUTO || a.K == 4096 ||
+       (epi != ZMI_EPI_SWIGLU && epi != ZMI_EPI_RESIDUAL && epi != ZMI_EPI_F32)))
+    return zmi_fail_msg("gemv: fp8 weights need w_exp (8-byte aligned) and are built for the plain / LayerNorm prologue, "
+                        "K = 512, 1024, 2048 or 8192 and the SWIGLU, RESIDUAL and F32 epilogues");
   hipStream_t s = (hipStream_t)stream;
   hipError_t e;
   switch (epi) {

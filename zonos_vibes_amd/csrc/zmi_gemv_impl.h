@@ -237,13 +237,43 @@ __device__ __forceinline__ void epilogue(const ZmiGemvArgs& a, const ColSum& col
   }
 }
 
-template <int G, int W, int NL, int RT, int PRO, int EPI, int NTW, int FUSE = 0>
+// Weight-only FP8 (FMT == ZMI_WFMT_FP8, layout M8F8): W[n][k] = 2^e[n] q[n][k] with q OCP E4M3. A 64-k x 8-column
+// chunk is 512 B and a lane's 16-byte load holds its 8 weights of chunk 2p (dwords 0, 1) and of chunk 2p + 1 (dwords
+// 2, 3), in the k order of M8. The bytes become the bf16 B operand in registers (exact: E4M3 has 3 mantissa bits)
+// and the products, the k-segments and the segment order are those of the bf16 form; the column's power of two
+// scales its finished fp32 sum before any epilogue sees it. Every step being exact or scale-invariant, the result
+// is the bf16 form's on the dequantised weights 2^e q, bit for bit (away from fp32 subnormal sums).
+__device__ __forceinline__ uint32_t fp8x2_to_bf16x2(uint32_t d, bool hi) {
+  // two E4M3 bytes (the low or the high half of d) -> two fp32 -> their high halves
+  const auto f = hi ? __builtin_amdgcn_cvt_pk_f32_fp8((int)d, true) : __builtin_amdgcn_cvt_pk_f32_fp8((int)d, false);
+  // v_perm_b32: bytes 2, 3 of f[0] (selectors 2, 3) below bytes 2, 3 of f[1] (selectors 6, 7)
+  return __builtin_amdgcn_perm(__float_as_uint(f[1]), __float_as_uint(f[0]), 0x07060302u);
+}
+__device__ __forceinline__ bf16x8_t fp8x8_to_bf16x8(uint32_t d0, uint32_t d1) {
+  const u32x4_t v = {fp8x2_to_bf16x2(d0, false), fp8x2_to_bf16x2(d0, true), fp8x2_to_bf16x2(d1, false),
+                     fp8x2_to_bf16x2(d1, true)};
+  return __builtin_bit_cast(bf16x8_t, v);
+}
+// 2^e of column c (0..7) of a group from its 8 int8 exponents; |e| <= 119 (quant.py), so the float is normal
+__device__ __forceinline__ float fp8_col_scale(const uint2& ex, int c) {
+  const uint32_t w = c < 4 ? ex.x : ex.y;
+  const int e = (int)(w << (24 - 8 * (c & 3))) >> 24;
+  return __uint_as_float((uint32_t)(e + 127) << 23);
+}
+
+template <int G, int W, int NL, int RT, int PRO, int EPI, int NTW, int FUSE = 0, int FMT = ZMI_WFMT_BF16>
 __device__ __forceinline__ void gemv_body(const ZmiGemvArgs& a, int n_cb, int n_rt, int b, char* smem,
                                           const QkvFuse& fz, int rpw = 1) {
   constexpr int K = W * NL * 64;
   constexpr int KC = K / 64;
   constexpr int NWV = G * W;
   constexpr int XROW = Img<K>::XROW;
+  constexpr bool F8 = FMT == ZMI_WFMT_FP8;
+  constexpr int CHB = F8 ? 512 : 1024;    // bytes of a 64-k x 8-column weight chunk
+  constexpr int NWL = F8 ? NL / 2 : NL;   // 16-byte weight loads per lane
+  static_assert(FMT == ZMI_WFMT_BF16 || F8, "weight format");
+  static_assert(!F8 || (NL % 2 == 0 && FUSE == 0 && (PRO == PRO_PLAIN || PRO == PRO_LN)),
+                "fp8 weights: the MLP projections' plain / LayerNorm launches");
   static_assert(RT == 8 || RT == 16, "row tile");
   static_assert(!FUSE || EPI == ZMI_EPI_QKV || EPI == ZMI_EPI_STORE || FUSE == 3, "in-launch hand-off: QKV or plain store");
   static_assert(FUSE != 2 || NTW, "the store hand-off runs on single-tile (decode) launches");
@@ -343,19 +373,27 @@ __device__ __forceinline__ void gemv_body(const ZmiGemvArgs& a, int n_cb, int n_
   };
   if (FUSE != 3) stage_rows(true, row0, rows, X);  // FUSE 3: the rows come from the attention's granules (below)
   stage_epi();
+  // fp8: the group's 8 column exponents, one 8-byte load per epilogue lane, older than the weights like the
+  // epilogue operands
+  uint2 wexp = {0u, 0u};
+  if constexpr (F8) {
+    if (ew) wexp = *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(a.w_exp) + col0);
+  }
   __builtin_amdgcn_sched_barrier(0);
   // (2) the whole weight slice of this lane, in flight at once: one buffer descriptor per wave
   // (wave-uniform base), lane offset in the VGPR, chunk offset j KiB folded into the instruction
   // (cdna_hip_programming.md T8). Non-temporal when each weight is read once (one row tile).
-  const char* wbase = reinterpret_cast<const char*>(a.W) + ((size_t)g * KC + wk * NL) * 1024;
+  // fp8: half the bytes, so NWL = NL / 2 loads of two chunks each.
+  const char* wbase = reinterpret_cast<const char*>(a.W) + ((size_t)g * KC + wk * NL) * CHB;
   const __amdgpu_buffer_rsrc_t wrsrc =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(wbase), (short)0, NL * 1024, 0x00020000);
-  u32x4_t wf[NL];
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(wbase), (short)0, NL * CHB, 0x00020000);
+  u32x4_t wf[NWL];
 #pragma unroll
-  for (int j = 0; j < NL; ++j) wf[j] = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, lane * 16, j * 1024, NTW ? 2 : 0);
+  for (int j = 0; j < NWL; ++j) wf[j] = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, lane * 16, j * 1024, NTW ? 2 : 0);
   __builtin_amdgcn_sched_barrier(0);
   ZMI_GSTAMP(1);
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NL) : "memory");  // DMA pieces + epilogue operands landed
+  // DMA pieces + epilogue operands landed: everything but this lane's NWL weight loads
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NWL) : "memory");
   // single-tile QKV launches (every decode step): the epilogue's RoPE cos / sin pair, issued now that the row's
   // position has landed, so it arrives under the LayerNorm and the MFMA chain instead of after them
   float2 rope_cs = {1.f, 0.f};
@@ -710,7 +748,11 @@ __device__ __forceinline__ void gemv_body(const ZmiGemvArgs& a, int n_cb, int n_
     for (int j = 0; j < NL; ++j) {
       const uint4 x0 = *reinterpret_cast<const uint4*>(xa + j * 64);
       const uint4 x1 = *reinterpret_cast<const uint4*>(xa + j * 64 + 32);
-      const bf16x8_t wv = __builtin_bit_cast(bf16x8_t, wf[j]);
+      bf16x8_t wv;
+      if constexpr (F8)  // the raw bytes stay in the registers; every row tile converts them again
+        wv = fp8x8_to_bf16x8(wf[j >> 1][2 * (j & 1)], wf[j >> 1][2 * (j & 1) + 1]);
+      else
+        wv = __builtin_bit_cast(bf16x8_t, wf[j]);
       acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, x0), wv, acc0, 0, 0, 0);
       acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, x1), wv, acc1, 0, 0, 0);
     }
@@ -737,6 +779,7 @@ __device__ __forceinline__ void gemv_body(const ZmiGemvArgs& a, int n_cb, int n_
       float v = red[((gi * W) * 8 + c) * RT + r];
 #pragma unroll
       for (int w = 1; w < W; ++w) v += red[((gi * W + w) * 8 + c) * RT + r];
+      if constexpr (F8) v *= fp8_col_scale(wexp, c);  // exact: a power of two
       return v;
     };
     epilogue<EPI, RT, FUSE>(a, colsum, lane, rows, row0, g, res_pre, q_pos, q_kvr, fz, act_rows,
@@ -758,6 +801,20 @@ template <int G, int W, int NL, int RT, int PRO, int EPI, int NTW>
 __global__ __launch_bounds__(G * W * 64) void gemv_kernel(const ZmiGemvArgs a, int n_cb, int n_rt, int rpw) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   gemv_body<G, W, NL, RT, PRO, EPI, NTW>(a, n_cb, n_rt, blockIdx.x, smem, QkvFuse{nullptr, 0}, rpw);
+}
+// the same launch over fp8 weights (a kernel of its own name: the bf16 kernels keep theirs in traces and profiles)
+template <int G, int W, int NL, int RT, int PRO, int EPI, int NTW>
+__global__ __launch_bounds__(G * W * 64) void gemv_kernel_f8(const ZmiGemvArgs a, int n_cb, int n_rt, int rpw) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  gemv_body<G, W, NL, RT, PRO, EPI, NTW, 0, ZMI_WFMT_FP8>(a, n_cb, n_rt, blockIdx.x, smem, QkvFuse{nullptr, 0}, rpw);
+}
+
+template <int FMT, int... A>
+constexpr auto gemv_fn() {  // the kernel of a weight format (only the one asked for is instantiated)
+  if constexpr (FMT == ZMI_WFMT_FP8)
+    return &gemv_kernel_f8<A...>;
+  else
+    return &gemv_kernel<A...>;
 }
 
 // s_waitcnt vmcnt(n) as the builtin (gfx9 encoding, expcnt / lgkmcnt left at their maxima): unlike an asm
@@ -1047,10 +1104,10 @@ inline int groups_for(const ZmiGemvArgs& a, const Shape& s) {
   return (a.K == 2048 && a.N / 8 >= 384 && (a.ln_w != nullptr || a.pro != ZMI_PRO_AUTO || a.M > 4)) ? 2 : 1;
 }
 
-template <int G, int W, int NL, int RT, int PRO, int EPI, int NTW>
+template <int G, int W, int NL, int RT, int PRO, int EPI, int NTW, int FMT = ZMI_WFMT_BF16>
 hipError_t launch_p(const ZmiGemvArgs& a, hipStream_t s) {
   constexpr int K = W * NL * 64;
-  auto fn = gemv_kernel<G, W, NL, RT, PRO, EPI, NTW>;
+  auto fn = gemv_fn<FMT, G, W, NL, RT, PRO, EPI, NTW>();
   const int n_cb = (a.N / 8 + G - 1) / G;
   const int n_rt = (a.M + RT - 1) / RT;
   size_t lds = Img<K>::bytes(a.M < RT ? a.M : RT, G * W, RT, PRO);
@@ -1075,6 +1132,16 @@ hipError_t launch_p(const ZmiGemvArgs& a, hipStream_t s) {
   if (blocks > 0x7fffffff) return hipErrorInvalidValue;
   hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(G * W * 64), lds, s, a, n_cb, n_rt, rpw);
   return hipGetLastError();
+}
+
+// fp8 weights (ZMI_WFMT_FP8): LayerNorm'd or plain rows, one tile (non-temporal) or the row-tile loop
+template <int G, int W, int NL, int RT, int EPI>
+hipError_t launch_g8(const ZmiGemvArgs& a, hipStream_t s) {
+  constexpr int F = ZMI_WFMT_FP8;
+  const bool once = a.M <= RT;
+  if (a.ln_w != nullptr)
+    return once ? launch_p<G, W, NL, RT, PRO_LN, EPI, 1, F>(a, s) : launch_p<G, W, NL, RT, PRO_LN, EPI, 0, F>(a, s);
+  return once ? launch_p<G, W, NL, RT, PRO_PLAIN, EPI, 1, F>(a, s) : launch_p<G, W, NL, RT, PRO_PLAIN, EPI, 0, F>(a, s);
 }
 
 template <int G, int W, int NL, int RT, int EPI>
@@ -1127,6 +1194,25 @@ hipError_t launch(const ZmiGemvArgs& a, hipStream_t s) {
   Shape sh;
   if (!shape_for(a.K, a.ln_w != nullptr, &sh)) return hipErrorInvalidValue;
   const int g = groups_for(a, sh);
+  if (a.w_fmt == ZMI_WFMT_FP8) {
+    // fp8 weights run gemv_body's tile loop for every M: the many-row form below (and the split-K GEMM) read bf16
+    // weights only. All forms agree bit for bit, so this costs many-row speed, never bits.
+    if constexpr (EPI == ZMI_EPI_SWIGLU || EPI == ZMI_EPI_RESIDUAL || EPI == ZMI_EPI_F32) {
+      if (a.pro != ZMI_PRO_AUTO) return hipErrorInvalidValue;
+      if (g == 4 && sh.W == 4 && sh.NL == 8 && sh.RT == 16 && a.M > sh.RT && a.ln_w == nullptr)
+        return launch_p<4, 4, 8, 16, PRO_PLAIN, EPI, 0, ZMI_WFMT_FP8>(a, s);
+#define ZMI_SHAPE8(G_, W_, NL_, RT_) \
+  if (g == G_ && sh.W == W_ && sh.NL == NL_ && sh.RT == RT_) return launch_g8<G_, W_, NL_, RT_, EPI>(a, s);
+      ZMI_SHAPE8(1, 2, 4, 16)
+      ZMI_SHAPE8(1, 4, 4, 16)
+      ZMI_SHAPE8(1, 4, 8, 16)
+      ZMI_SHAPE8(2, 4, 8, 16)
+      ZMI_SHAPE8(1, 8, 16, 8)
+      ZMI_SHAPE8(2, 8, 16, 8)
+#undef ZMI_SHAPE8
+    }
+    return hipErrorInvalidValue;
+  }
   if (a.K == 2048 && a.M > GR_RT && a.ln_w == nullptr && a.pro == ZMI_PRO_AUTO && a.groups == 0 &&
       zmi_option(ZMI_OPT_GEMM_ROWS) && rows_form(a.M, a.N))
     return (zmi_option(ZMI_OPT_GEMM_ROWS) & 2) ? launch_rows<EPI, 1, true>(a, s) : launch_rows<EPI, 2, false>(a, s);

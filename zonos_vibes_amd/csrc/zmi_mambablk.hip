@@ -158,6 +158,7 @@ extern "C" int zmi_mamba_block_pf(const ZmiGemvArgs* in_proj, const ZmiMamba2Arg
   const ZmiMamba2Args& s = *step;
   if (a.K != 2048 || a.pro != ZMI_PRO_ADDLN || !a.ln_w || !a.ln_b || !a.aux || a.ld_aux % 8 || a.res_out == a.aux)
     return zmi_fail_msg("mamba_block: in_proj must be the ADDLN GEMV with K = 2048");
+  if (a.w_fmt != ZMI_WFMT_BF16) return zmi_fail_msg("mamba_block: bf16 weights only");
   if (a.M < 1 || a.M > IRT || s.M != a.M) return zmi_fail_msg("mamba_block: 1 <= M <= 16 rows, the same in both");
   if (s.headdim != MB_HD || s.d_state != MB_DS || s.d_conv != MB_DC || s.ngroups != 1 || s.nheads <= 0 ||
       s.d_ssm != s.nheads * MB_HD)

@@ -20,7 +20,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, quant
 from . import synthetic as syn
 from .config import EMB_VOCAB, HEAD_VOCAB, N_CODEBOOKS, ROPE_TABLE_LEN, ZonosConfig
 
@@ -28,6 +28,7 @@ HEADS_N = N_CODEBOOKS * 1026            # 9 heads x (1025 + 1 pad row), model.py
 HEADS_N_PAD = (HEADS_N + 15) // 16 * 16
 PREFILL_BATCH_ROWS = 2048  # rows of one batched prefill pass (prefill_many): 6 C2-sized utterances (2 x 161)
 BLK_ROWS_MAX = 16  # rows zmi_attn_block takes (one MFMA row tile, include/zonos_hip.h)
+WEIGHT_FORMATS = ("bf16", "fp8")  # the engines' `weights` argument (fp8: quant.py)
 
 
 def rope_table(hd: int, n: int = ROPE_TABLE_LEN) -> torch.Tensor:
@@ -103,10 +104,15 @@ class HipEngine:
     prefill_batch = True  # prefill_many packs several slots into one pass (the hybrid's scan does not)
 
     def __init__(self, cfg: ZonosConfig, device="cuda", max_slots: int = 1, max_seqlen: int = 2048,
-                 max_prefill: int = 512):
+                 max_prefill: int = 512, weights: str = "bf16"):
         bb = cfg.backbone
+        check_weights(weights, bool(bb.ssm_cfg))
         if bb.ssm_cfg and not self.hybrid:
             raise ValueError("hybrid (mamba-ssm) configs run on HybridEngine (make_engine picks it)")
+        # "bf16", or "fp8": mlp.fc1 / mlp.fc2 of every layer as E4M3 bytes with one power-of-two exponent per
+        # output row (quant.py); every other tensor stays bf16. The fp8 engine computes exactly what the bf16
+        # engine computes on the dequantised weights (dequantized_state_dict_overrides).
+        self.weights = weights
         self.cfg = cfg
         self.dev = torch.device(device)
         self.d, self.L, self.H, self.Hkv = bb.d_model, bb.n_layer, bb.num_heads, bb.num_heads_kv
@@ -272,8 +278,37 @@ class HipEngine:
         _lib.check(self.lib.zmi_pack_weight(w.data_ptr(), out.data_ptr(), n_src, k, n_pad, mode, self.sptr), "pack")
         return out
 
-    def load_state_dict(self, sd: dict):
-        """Reference state_dict names (model.py:22-51, _torch.py:52-152); heads [1025, d] or [1026, d]."""
+    def _pack_mlp(self, w: torch.Tensor, n_pad: int, mode: int = _lib.PACK_IDENTITY) -> torch.Tensor:
+        """An MLP projection in the engine's weight format. bf16: _pack. fp8: ONE uint8 tensor of n_pad * k E4M3
+        bytes in layout M8F8 followed by the n_pad int8 exponents of the packed columns (quant.pack_m8f8): the
+        launch arguments (_gemv) and the prefetch ranges take both from it."""
+        if self.weights != "fp8":
+            return self._pack(w, n_pad, mode)
+        q, e = quant.quantize_fp8(w.to(self.dev, torch.bfloat16))
+        packed, ep = quant.pack_m8f8(q, e, n_pad, mode)
+        return torch.cat([packed, ep.view(torch.uint8)])
+
+    def dequantized_state_dict_overrides(self) -> dict:
+        """{state_dict name: bf16 [n][k]} of every quantised tensor, dequantised: a bf16 engine loaded with the same
+        state dict and these in place of the originals computes exactly what this engine computes. Empty for bf16."""
+        out = {}
+        if self.weights == "fp8":
+            with torch.cuda.stream(self.stream):
+                for i, lw in enumerate(self.w["layers"]):
+                    for key, n, k, mode in (("fc1", 2 * self.F, self.d, _lib.PACK_SWIGLU),
+                                            ("fc2", self.d, self.F, _lib.PACK_IDENTITY)):
+                        t = lw[key]
+                        q, e = quant.unpack_m8f8(t[: n * k], t[n * k:].view(torch.int8), n, k, mode)
+                        out[f"backbone.layers.{i}.mlp.{key}.weight"] = quant.dequantize_fp8(q, e)
+            self.stream.synchronize()
+        return out
+
+    def load_state_dict(self, sd: dict, consume: bool = False):
+        """Reference state_dict names (model.py:22-51, _torch.py:52-152); heads [1025, d] or [1026, d].
+        With weights="fp8" the MLP projections are quantised and packed one at a time, so the engine holds the
+        bf16 form of one projection beside the fp8 copies, never of all of them; consume=True also drops each
+        MLP weight from `sd` once it is packed (a caller that owns the dict, as init_synthetic does)."""
+        take = sd.pop if consume else sd.__getitem__
         bf = lambda t: t.to(self.dev, torch.bfloat16).contiguous()  # noqa: E731
         with torch.cuda.stream(self.stream):
             w = {}
@@ -288,8 +323,8 @@ class HipEngine:
                     qkv=self._pack(sd[p + "mixer.in_proj.weight"], qkv_n),
                     out=self._pack(sd[p + "mixer.out_proj.weight"], self.d),
                     ln2_w=bf(sd[p + "norm2.weight"]), ln2_b=bf(sd[p + "norm2.bias"]),
-                    fc1=self._pack(sd[p + "mlp.fc1.weight"], 2 * self.F, _lib.PACK_SWIGLU),
-                    fc2=self._pack(sd[p + "mlp.fc2.weight"], self.d)))
+                    fc1=self._pack_mlp(take(p + "mlp.fc1.weight"), 2 * self.F, _lib.PACK_SWIGLU),
+                    fc2=self._pack_mlp(take(p + "mlp.fc2.weight"), self.d)))
             w["layers"] = layers
             w["nf_w"], w["nf_b"] = bf(sd["backbone.norm_f.weight"]), bf(sd["backbone.norm_f.bias"])
             if "heads.0.weight" in sd:
@@ -304,6 +339,14 @@ class HipEngine:
         self._build_plan()
 
     def init_synthetic(self, seed: int = 0, zero_eos: bool = False, eos_row_scale: float | None = None):
+        """Load the synthetic weights of synthetic.zonos_specs (synthetic_state_dict)."""
+        sd = self.synthetic_state_dict(seed, zero_eos, eos_row_scale)
+        if self.weights == "fp8":
+            self.load_state_dict(sd, consume=True)
+        else:
+            self.load_state_dict(sd)
+
+    def synthetic_state_dict(self, seed: int = 0, zero_eos: bool = False, eos_row_scale: float | None = None) -> dict:
         """Materialise the synthetic weights of synthetic.zonos_specs on the GPU (bit-identical to numpy)."""
         sd = {}
         with torch.cuda.stream(self.stream):
@@ -317,12 +360,15 @@ class HipEngine:
                 h0[1024] = 0
             if eos_row_scale is not None:
                 h0[1024] = (h0[1024].float() * eos_row_scale).to(torch.bfloat16)
-        self.load_state_dict(sd)
+        self.stream.synchronize()
+        return sd
 
     # ------------------------------------------------------------------ launch plan
     def _gemv(self, W, X, M, N, K, epi, out, ldo, n_valid=None, ln=None, kv=None, row_kv=None, row_pos=None):
         a = _lib.GemvArgs()
         a.W, a.X, a.M, a.N, a.K, a.ldx = W.data_ptr(), X.data_ptr(), M, N, K, K
+        if W.dtype == torch.uint8:  # an fp8 projection (_pack_mlp): N x K E4M3 bytes, then the N column exponents
+            a.w_fmt, a.w_exp = _lib.WFMT_FP8, W.data_ptr() + N * K
         if ln is not None:
             a.ln_w, a.ln_b = ln[0].data_ptr(), ln[1].data_ptr()
         a.eps = self.eps
@@ -346,7 +392,9 @@ class HipEngine:
     def _use_splitk(self, a, epi) -> bool:
         lo = {8192: self.splitk_rows, 2048: self.splitk_o_rows, 4096: self.splitk_m_rows}.get(a.K, 0)
         want = _lib.EPI_STORE if a.K == 4096 else _lib.EPI_RESIDUAL  # 4096: the hybrid's Mamba2 out_proj (d_ssm)
+        # (fp8 weights: the split-K GEMM reads bf16 only; gemv_body's tile loop gives the same bits)
         return (lo > 0 and a.M >= lo and epi == want and not a.ln_w and a.pro == _lib.PRO_AUTO
+                and a.w_fmt == _lib.WFMT_BF16
                 and a.N % 64 == 0 and a.n_valid == a.N
                 and a.M * a.N * (8 if a.K == 8192 else 4) <= self.splitk_part.numel())
 
@@ -441,7 +489,7 @@ class HipEngine:
                         else:
                             nw = lw["fc1"]
                         pf.ptr[1] = nw.data_ptr()
-                        pf.bytes[1] = min(nw.numel() * 2, int(self.prefetch_fc1_mb * 2 ** 20))
+                        pf.bytes[1] = min(nw.numel() * nw.element_size(), int(self.prefetch_fc1_mb * 2 ** 20))
                         pf.sink, pf.blocks = self.blk_err[2:].data_ptr(), self.prefetch_blocks
                     o_fused = self._gemv(lw["out"], self.attn, rows, d, qd, _lib.EPI_RESIDUAL, self.x, d)[0] if oproj else None
                     plan.append(("attnblk", (qkv[0], i, pf, self._block_slices(form), o_fused)))
@@ -452,7 +500,8 @@ class HipEngine:
                         apf = _lib.Prefetch()
                         apf.ptr[0], apf.bytes[0] = lw["out"].data_ptr(), lw["out"].numel() * 2
                         apf.ptr[1] = lw["fc1"].data_ptr()
-                        apf.bytes[1] = min(lw["fc1"].numel() * 2, int(self.attn_prefetch_fc1_mb * 2 ** 20))
+                        apf.bytes[1] = min(lw["fc1"].numel() * lw["fc1"].element_size(),
+                                           int(self.attn_prefetch_fc1_mb * 2 ** 20))
                         apf.sink, apf.blocks = self.blk_err[2:].data_ptr(), self.attn_prefetch_blocks
                     plan.append(("attn", (i, apf)))
                 o_item = self._gemv(lw["out"], self.attn, rows, d, qd, _lib.EPI_RESIDUAL, self.x, d)
@@ -832,10 +881,21 @@ class HipEngine:
             self.row_pos[2 * slot: 2 * slot + 2] = -1
 
 
+def check_weights(weights: str, hybrid: bool) -> None:
+    """The engines' `weights` argument: "bf16", or "fp8" (transformer backbones: Zonos-v0.1-hybrid has no MLPs, and
+    the hybrid's Mamba2 projections are not built for fp8)."""
+    if weights not in WEIGHT_FORMATS:
+        raise ValueError(f"weights={weights!r}: expected one of {WEIGHT_FORMATS}")
+    if weights != "bf16" and hybrid:
+        raise NotImplementedError(f'weights="{weights}" is built for the transformer backbone\'s MLP projections; '
+                                  "the hybrid engine takes bf16 weights only")
+
+
 def make_engine(cfg: ZonosConfig, device="cuda", max_slots: int = 1, max_seqlen: int = 2048,
-                max_prefill: int = 512) -> HipEngine:
+                max_prefill: int = 512, weights: str = "bf16") -> HipEngine:
     """The engine for a config's backbone: HipEngine (transformer) or HybridEngine (Mamba2 + MHA)."""
+    check_weights(weights, bool(cfg.backbone.ssm_cfg))
     if cfg.backbone.ssm_cfg:
         from .hybrid import HybridEngine
         return HybridEngine(cfg, device, max_slots, max_seqlen, max_prefill)
-    return HipEngine(cfg, device, max_slots, max_seqlen, max_prefill)
+    return HipEngine(cfg, device, max_slots, max_seqlen, max_prefill, weights)

@@ -32,12 +32,15 @@ def _draw_seed() -> int:
 
 class Zonos:
     def __init__(self, config: ZonosConfig, device="cuda", max_slots: int = 1, max_seqlen: int = 2048,
-                 max_prefill: int = 512, autoencoder: DACAutoencoder | None = None):
+                 max_prefill: int = 512, autoencoder: DACAutoencoder | None = None, weights: str = "bf16"):
+        """weights: "bf16", or "fp8" for weight-only E4M3 MLP projections (transformer backbones; quant.py): the
+        decode step then streams 0.6 of the bytes and computes exactly the bf16 model on the dequantised weights."""
         self.config = config
         self.eos_token_id = config.eos_token_id
         self.masked_token_id = config.masked_token_id
         self._device = torch.device(device)
-        self.engine = make_engine(config, device, max_slots, max_seqlen, max_prefill)
+        self.weights = weights
+        self.engine = make_engine(config, device, max_slots, max_seqlen, max_prefill, weights)
         self.autoencoder = autoencoder if autoencoder is not None else DACAutoencoder(device)
         pcc = config.prefix_conditioner
         self.prefix_conditioner = (PrefixConditioner(pcc.conditioners, config.backbone.d_model, device, pcc.projection)
@@ -101,7 +104,7 @@ class Zonos:
         if slots > e.S or seqlen > e.smax or prefill > e.max_prefill:
             w = e.w
             self.engine = make_engine(self.config, self._device, max(slots, e.S), max(seqlen, e.smax),
-                                      max(prefill, e.max_prefill))
+                                      max(prefill, e.max_prefill), self.weights)
             self.engine.w = w
             self.engine._build_plan()
 
@@ -458,7 +461,8 @@ class Zonos:
     def __repr__(self):
         bb = self.config.backbone
         kind = "hybrid" if bb.is_hybrid else "transformer"
-        return f"Zonos(hip {kind}, d={bb.d_model}, layers={bb.n_layer}, heads={bb.num_heads}/{bb.num_heads_kv})"
+        return (f"Zonos(hip {kind}, d={bb.d_model}, layers={bb.n_layer}, heads={bb.num_heads}/{bb.num_heads_kv}, "
+                f"weights={self.weights})")
 
 
 __all__ = ["Zonos", "DACAutoencoder", "N_CODEBOOKS"]
