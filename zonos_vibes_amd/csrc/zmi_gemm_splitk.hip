@@ -20,9 +20,6 @@
 
 namespace {
 
-using zmi_gemv::dma_piece;
-using zmi_gemv::ror8;
-
 // K segments are the GEMV's wave segments: K = 8192 (fc2) W = 8 x 16 chunks, K = 4096 (the hybrid's Mamba2
 // out_proj over d_ssm) W = 4 x 16, K = 2048 (out_proj) W = 4 x 8 (zmi_gemv_impl.h shape_for)
 template <int K>
@@ -45,6 +42,7 @@ constexpr int DNWV = 4, DNT = DNWV * 64;
 template <int K, bool DN, int RTS>
 __global__ __launch_bounds__(DN ? DNT : NT) void splitk_kernel(const ZmiGemvArgs a, float* part, int n_cb, int rpg) {
   using S = Shape<K>;
+  using namespace zmi_gemv;  // dma_piece and the row arithmetic (zmi_gemv_row.h)
   constexpr int NSEG = S::NSEG, KS = S::KS, NL = S::NL, KC = S::KC, SROW = S::SROW, TILE_BYTES = S::TILE_BYTES;
   constexpr int NW = DN ? DNWV : NWV;  // waves
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -52,8 +50,8 @@ __global__ __launch_bounds__(DN ? DNT : NT) void splitk_kernel(const ZmiGemvArgs
   const int seg = b / n_cb, cb = b - seg * n_cb;  // consecutive blocks: one segment, neighbouring columns
   const int t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-  // the wave's group (DN: the group of lane l's column, 2 wave + ((l >> 3) & 1), of the wave's pair)
-  const int g = DN ? cb * NWV + 2 * wave + ((lane >> 3) & 1) : cb * NWV + wave;
+  // the wave's group (DN: the group of lane l's column, 2 wave + dn_member(l), of the wave's pair)
+  const int g = DN ? cb * NWV + 2 * wave + dn_member(lane) : cb * NWV + wave;
   const int M = a.M, N = a.N;
   const int rt0 = rg * rpg, n_rt = min((M + RT - 1) / RT, rt0 + rpg);
   if (rt0 >= n_rt) return;
@@ -71,26 +69,15 @@ __global__ __launch_bounds__(DN ? DNT : NT) void splitk_kernel(const ZmiGemvArgs
     }
   };
   stage(0, 0);
-  // the wave's weights for this segment: group g, chunks seg * NL .. + NL - 1 (layout M8), all in flight
-  // (DN: k-half h of lane l's column = M8 lane (l & 7) + 8 h + 16 (l >> 4) of group g's chunk)
+  // the wave's weights for this segment: group g, chunks seg * NL .. + NL - 1 (layout M8), all in flight, non-temporal
+  // (DN: the descriptor starts at the column block's first group, the lane's group g at an offset from it)
   constexpr int NH = DN ? 2 : 1;
   u32x4_t wf[NH][NL];
-  if constexpr (DN) {
-    const char* wbase = reinterpret_cast<const char*>(a.W) + ((size_t)cb * NWV * KC + seg * NL) * 1024;
-    const __amdgpu_buffer_rsrc_t wrsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(wbase), (short)0, NWV * KC * 1024, 0x00020000);
-    const int vo = (g - cb * NWV) * KC * 1024 + ((lane & 7) + 16 * (lane >> 4)) * 16;
-#pragma unroll
-    for (int j = 0; j < NL; ++j)
-#pragma unroll
-      for (int h = 0; h < 2; ++h) wf[h][j] = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, vo + 128 * h, j * 1024, 2);
-  } else {
-    const char* wbase = reinterpret_cast<const char*>(a.W) + ((size_t)g * KC + seg * NL) * 1024;
-    const __amdgpu_buffer_rsrc_t wrsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(wbase), (short)0, NL * 1024, 0x00020000);
-#pragma unroll
-    for (int j = 0; j < NL; ++j) wf[0][j] = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, lane * 16, j * 1024, 2);
-  }
+  if constexpr (DN)
+    load_weights_dn<NL, 2>(reinterpret_cast<const char*>(a.W) + ((size_t)cb * NWV * KC + seg * NL) * 1024, NWV * KC * 1024,
+                           (g - cb * NWV) * KC * 1024, lane, wf);
+  else
+    load_weights_m8<NL, 2>(reinterpret_cast<const char*>(a.W) + ((size_t)g * KC + seg * NL) * 1024, NL * 1024, lane, wf[0]);
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NH * NL) : "memory");  // the first stage's pieces (issued before)
   for (int st = 0; st < n_st; ++st) {
     __syncthreads();  // stage st landed for every wave's pieces; the other buffer is free
@@ -104,21 +91,15 @@ __global__ __launch_bounds__(DN ? DNT : NT) void splitk_kernel(const ZmiGemvArgs
       f32x4_t acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
       const int ar = min(lane & 15, rows - 1);
       const bf16_t* xa = xs + ar * SROW + (lane >> 4) * 8;
-#pragma unroll
-      for (int j = 0; j < NL; ++j) {
-        const uint4 x0 = *reinterpret_cast<const uint4*>(xa + j * 64);
-        const uint4 x1 = *reinterpret_cast<const uint4*>(xa + j * 64 + 32);
-        const bf16x8_t w0 = __builtin_bit_cast(bf16x8_t, wf[0][j]), w1 = __builtin_bit_cast(bf16x8_t, wf[NH - 1][j]);
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, x0), w0, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, x1), w1, acc1, 0, 0, 0);
-      }
-      // segment sum = k-half 0 (tile columns 0..7) + k-half 1 (columns 8..15 moved down): element q of lane l
-      // is row 4 (l >> 4) + q, column l & 15 (DN: both halves in place, column l & 15 of the pair)
-      const int c = lane & 15, rb = (lane >> 4) * 4;
+      if constexpr (DN)
+        chain_dn<NL>(xa, wf, acc0, acc1);
+      else
+        chain_m8<NL, false>(xa, wf[0], acc0, acc1);
+      const SegPos sp = segment_pos<DN>(lane);  // the segment's fp32 sums of the live rows (DN: g is the lane's group)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const float v = DN ? acc0[q] + acc1[q] : acc0[q] + ror8(acc1[q]);
-        if ((DN || c < 8) && rb + q < rows) part[((size_t)seg * M + row0 + rb + q) * N + g * 8 + (c & 7)] = v;
+        const float v = segment_value<DN>(acc0, acc1, q);
+        if (sp.live && sp.rb + q < rows) part[((size_t)seg * M + row0 + sp.rb + q) * N + g * 8 + (sp.c & 7)] = v;
       }
     }
     if (st + 1 < n_st) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the next stage's pieces

@@ -47,7 +47,7 @@ extern "C" int zmi_gemv_launch(const ZmiGemvArgs* args, int epi, void* stream) {
   const ZmiGemvArgs& a = *args;
   zmi_gemv::Shape sh;
   if (a.N % 8) return zmi_fail_msg("gemv: N must be a multiple of 8");
-  if (!zmi_gemv::shape_for(a.K, a.ln_w != nullptr, &sh))
+  if (!zmi_gemv::shape_for(a.K, &sh))
     return zmi_fail_msg("gemv: K must be 512, 1024, 2048, 4096 or 8192");
   if (a.M < 1) return zmi_fail_msg("gemv: M must be >= 1");
   if (a.ldx % 8) return zmi_fail_msg("gemv: ldx must be a multiple of 8 (16-byte rows)");

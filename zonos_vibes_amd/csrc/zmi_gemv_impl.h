@@ -3,31 +3,28 @@
 // out[m, n] = sum_k A[m, k] * W[n, k]   (nn.Linear, reference zonos/backbone/_torch.py:114-115,147-152,
 //                                        heads: zonos/model.py:100-101)
 //
-// One kernel for every row count M (decode: M = 2 x slots; prefill: M = 2 x prefill length), so a
-// row's result never depends on how many rows share the launch (batched output
-// must equal the reference's batch_size=1 output, model.py:194):
+// One kernel for every row count M (decode: M = 2 x slots; prefill: M = 2 x prefill length), so a row's result never
+// depends on how many rows share the launch (batched output must equal the reference's batch_size=1
+// output, model.py:194):
 //
-//  * a workgroup owns G groups of 8 output columns over the WHOLE K, and a tile of RT rows;
-//    W waves per group split K into fixed segments; every lane issues all of its weight loads
-//    (NL x 16 B, straight into VGPRs) before it needs the first one. Row tiles of one column
-//    block re-read the weights (from L2 when they run together: the block -> tile map below puts
-//    them on one XCD, consecutive in dispatch order; speed only, never correctness).
-//  * the products run on MFMA v_mfma_f32_16x16x32_bf16 with 8 real columns per 16-column tile:
-//    lane l of a 1 KiB weight chunk holds column 8g + (l & 7) at k = 64 kc + 32 ((l >> 3) & 1) +
-//    8 (l >> 4) .. +7 (layout "M8", zmi_pack_weight). Against the activation k-half 0 the
-//    tile's columns 0..7 are exact partial sums, against k-half 1 its columns 8..15 are; the
-//    other half of each tile is discarded. Each chunk therefore costs two MFMAs and no lane
-//    movement, and a tile carries up to 16 rows for the same cost as one.
-//  * fixed reduction order, independent of M and of the tile a row lands in: per wave a
-//    chain of MFMAs over its k-segment (k-half 0 and k-half 1 in two accumulators), their sum,
-//    then the W segment sums in wave order.
-//  * optional LayerNorm prologue (nn.LayerNorm, _torch.py:62,88,90): (row, part) tasks over the waves, fp32
-//    two-pass statistics, bf16-rounded output, the same arithmetic for every row.
+//  * a workgroup owns G groups of 8 output columns over the WHOLE K, and a tile of RT rows; W waves per group split K
+//    into fixed segments; every lane issues all of its weight loads (NL x 16 B, straight into VGPRs) before it needs
+//    the first one. Row tiles of one column block re-read the weights (from L2 when they run together: the block ->
+//    tile map puts them on one XCD, consecutive in dispatch order; speed only, never correctness).
+//  * the products run on MFMA v_mfma_f32_16x16x32_bf16 with 8 real columns per 16-column tile: lane l of a 1 KiB
+//    weight chunk holds column 8g + (l & 7) at k = 64 kc + 32 ((l >> 3) & 1) + 8 (l >> 4) .. +7 (layout "M8",
+//    zmi_pack_weight): each chunk costs two MFMAs (k-half 0 / 1) and no lane movement, and a tile carries up to 16 rows
+//    for the same cost as one.
+//  * fixed reduction order, independent of M and of the tile a row lands in: per wave a chain of MFMAs over its
+//    k-segment, their sum, then the W segment sums in wave order (the row arithmetic, zmi_gemv_row.h).
+//  * optional LayerNorm prologue (nn.LayerNorm, _torch.py:62,88,90): (row, part) tasks over the waves, fp32 two-pass
+//    statistics, bf16-rounded output, the same arithmetic for every row.
 //  * fused epilogues: bf16 store, residual add, RoPE + KV-cache write, SwiGLU, logits, raw f32.
 #pragma once
 #include <algorithm>
 #include "zmi_common.h"
 #include "zmi_kernels.h"
+#include "zmi_gemv_row.h"
 
 namespace zmi_gemv {
 
@@ -36,11 +33,6 @@ constexpr int PRO_PLAIN = 0, PRO_LN = 1, PRO_ADDLN = 2, PRO_GRMS = 3;
 // writes g; the same bits as GRMS, one third fewer activation bytes per workgroup)
 constexpr int PRO_GRMSG = 4;
 constexpr size_t LDS_MAX = 160 * 1024;  // gfx950 LDS per workgroup
-
-// DPP row_ror:8 — lane i of each 16-lane row reads lane (i + 8) & 15 of the same row
-__device__ __forceinline__ float ror8(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128, 0xf, 0xf, false));
-}
 
 __device__ __forceinline__ void dma_piece(const bf16_t* gsrc, bf16_t* ldp) {
   // one 1 KiB LDS-DMA piece (64 lanes x 16 B, lane-linear). Inline asm: the compiler does not
@@ -58,18 +50,36 @@ __device__ __forceinline__ void dma_piece(const bf16_t* gsrc, bf16_t* ldp) {
 
 // LDS image: rows of x at a stride of K + 8 bf16 (2K + 16 bytes: the 16 rows of an MFMA
 // A-fragment read fall on distinct 16-byte bank slots), the aux rows (ADDLN residual / GRMS z) at the
-// same stride, gamma (/ beta), then the segment sums.
+// same stride, gamma (/ beta), then the segment sums. Img owns the layout: the host sizes the launch (bytes) and the
+// kernel carves its pointers (View) from the same byte offsets, for `rows` staged rows and prologue `pro`.
 template <int K>
 struct Img {
-  static constexpr int XROW = K + 8;
-  static constexpr int GROW = K + 8;  // f32 gate rows (GRMS)
-  static size_t bytes(int rows, int nwv, int rt, int pro) {
-    const bool grms = pro == PRO_GRMS || pro == PRO_GRMSG;
-    const size_t gb = (pro == PRO_LN || pro == PRO_ADDLN) ? (size_t)4 * K : (grms ? (size_t)2 * K : 0);
-    const size_t aux = pro == PRO_ADDLN ? (size_t)rows * XROW * 2 : (grms ? (size_t)rows * GROW * 4 : 0);
-    return (size_t)rows * XROW * 2 + aux + gb + (size_t)nwv * 8 * rt * 4;
+  static constexpr int XROW = K + 8, GROW = K + 8;  // bf16 x / aux rows; f32 gate rows (GRMS)
+  __host__ __device__ static constexpr bool grms(int pro) { return pro == PRO_GRMS || pro == PRO_GRMSG; }
+  __host__ __device__ static constexpr size_t aux_off(int rows) { return (size_t)rows * XROW * 2; }
+  __host__ __device__ static constexpr size_t gamma_off(int rows, int pro) {
+    return aux_off(rows) + (size_t)rows * (pro == PRO_ADDLN ? XROW * 2 : (grms(pro) ? GROW * 4 : 0));
+  }
+  __host__ __device__ static constexpr size_t red_off(int rows, int pro) {  // after gamma (+ beta)
+    return gamma_off(rows, pro) + (size_t)K * ((pro == PRO_LN || pro == PRO_ADDLN) ? 4 : (grms(pro) ? 2 : 0));
+  }
+  __host__ __device__ static constexpr size_t bytes(int rows, int nwv, int rt, int pro) {
+    return red_off(rows, pro) + (size_t)nwv * 8 * rt * 4;
+  }
+  // x rows; aux rows (xa: ADDLN bf16 residual, xg: the same bytes as GRMS f32 gate / g rows); gamma; beta; segment sums
+  struct View {
+    bf16_t *xs, *xa, *gam, *bet;
+    float *xg, *red;
+  };
+  __device__ static View carve(char* smem, int rows, int pro) {
+    char *aux = smem + aux_off(rows), *gamma = smem + gamma_off(rows, pro);
+    return {reinterpret_cast<bf16_t*>(smem), reinterpret_cast<bf16_t*>(aux), reinterpret_cast<bf16_t*>(gamma),
+            reinterpret_cast<bf16_t*>(gamma) + K, reinterpret_cast<float*>(aux),
+            reinterpret_cast<float*>(smem + red_off(rows, pro))};
   }
 };
+template <int K>
+using View = typename Img<K>::View;
 
 // fp32 sum of one 8-element chunk of x + aux (ADDLN: layer_norm_fn's fp32 residual sum), or of its
 // squared deviations; pairs added as (a + b), the order of ln_chunk_sum and zmi_add_layernorm
@@ -135,10 +145,16 @@ struct QkvFuse {
   int l2_cols = 0;
 };
 
+// the RoPE cos / sin pair of q or k column n (an even column below (hq + hkv) hd) at position q_pos
+__device__ __forceinline__ const float2* rope_pair(const ZmiGemvArgs& a, int q_pos, int n) {
+  const int qcols = a.hq * a.hd, d = (n < qcols ? n : n - qcols) % a.hd;
+  return reinterpret_cast<const float2*>(a.rope + ((size_t)q_pos * (a.hd >> 1) + (d >> 1)) * 2);
+}
+
 // (6) fused epilogues of one group's 8 columns over a row tile, run by one wave; colsum(c, r) = the
-// group's finished column sum. Shared by every launch form (gemv_body, gemm_rows_kernel): the same bits.
-template <int EPI, int RT, int FUSE, class ColSum>
-__device__ __forceinline__ void epilogue(const ZmiGemvArgs& a, const ColSum& colsum, int lane, int rows, int row0,
+// group's finished column sum (ColSum). Shared by every launch form (gemv_body, gemm_rows_kernel): the same bits.
+template <int EPI, int RT, int FUSE, class Sum>
+__device__ __forceinline__ void epilogue(const ZmiGemvArgs& a, const Sum& colsum, int lane, int rows, int row0,
                                          int g, const uint32_t (&res_pre)[(8 * RT + 63) / 64], int q_pos, int q_kvr,
                                          const QkvFuse& fz, unsigned act_rows = ~0u, const float2* rope_pre = nullptr) {
   constexpr int NE = (8 * RT + 63) / 64;
@@ -198,11 +214,9 @@ __device__ __forceinline__ void epilogue(const ZmiGemvArgs& a, const ColSum& col
       const int qcols = a.hq * a.hd, kcols = a.hkv * a.hd;
       float x0 = bfround(colsum(c, r)), x1 = bfround(colsum(c + 1, r));
       if (n < qcols + kcols) {
-        const int d = (n < qcols ? n : n - qcols) % a.hd;
         // rope_pre: the cos / sin pair loaded by the caller before its LayerNorm (a load here is a memory round trip on
         // the decode step's critical path)
-        const float2 cs = rope_pre ? *rope_pre
-                                   : *reinterpret_cast<const float2*>(a.rope + ((size_t)q_pos * (a.hd >> 1) + (d >> 1)) * 2);
+        const float2 cs = rope_pre ? *rope_pre : *rope_pair(a, q_pos, n);
         const float co = cs.x, si = cs.y;
         const float r0 = x0 * co - x1 * si;
         const float r1 = x1 * co + x0 * si;
@@ -237,30 +251,355 @@ __device__ __forceinline__ void epilogue(const ZmiGemvArgs& a, const ColSum& col
   }
 }
 
-// Weight-only FP8 (FMT == ZMI_WFMT_FP8, layout M8F8): W[n][k] = 2^e[n] q[n][k] with q OCP E4M3. A 64-k x 8-column
-// chunk is 512 B and a lane's 16-byte load holds its 8 weights of chunk 2p (dwords 0, 1) and of chunk 2p + 1 (dwords
-// 2, 3), in the k order of M8. The bytes become the bf16 B operand in registers (exact: E4M3 has 3 mantissa bits)
-// and the products, the k-segments and the segment order are those of the bf16 form; the column's power of two
-// scales its finished fp32 sum before any epilogue sees it. Every step being exact or scale-invariant, the result
-// is the bf16 form's on the dequantised weights 2^e q, bit for bit (away from fp32 subnormal sums).
-__device__ __forceinline__ uint32_t fp8x2_to_bf16x2(uint32_t d, bool hi) {
-  // two E4M3 bytes (the low or the high half of d) -> two fp32 -> their high halves
-  const auto f = hi ? __builtin_amdgcn_cvt_pk_f32_fp8((int)d, true) : __builtin_amdgcn_cvt_pk_f32_fp8((int)d, false);
-  // v_perm_b32: bytes 2, 3 of f[0] (selectors 2, 3) below bytes 2, 3 of f[1] (selectors 6, 7)
-  return __builtin_amdgcn_perm(__float_as_uint(f[1]), __float_as_uint(f[0]), 0x07060302u);
-}
-__device__ __forceinline__ bf16x8_t fp8x8_to_bf16x8(uint32_t d0, uint32_t d1) {
-  const u32x4_t v = {fp8x2_to_bf16x2(d0, false), fp8x2_to_bf16x2(d0, true), fp8x2_to_bf16x2(d1, false),
-                     fp8x2_to_bf16x2(d1, true)};
-  return __builtin_bit_cast(bf16x8_t, v);
-}
-// 2^e of column c (0..7) of a group from its 8 int8 exponents; |e| <= 119 (quant.py), so the float is normal
-__device__ __forceinline__ float fp8_col_scale(const uint2& ex, int c) {
-  const uint32_t w = c < 4 ? ex.x : ex.y;
-  const int e = (int)(w << (24 - 8 * (c & 3))) >> 24;
-  return __uint_as_float((uint32_t)(e + 127) << 23);
+// ---- The phases of gemv_body, in the order it runs them: what each needs on entry and what it leaves.
+// (1) Activation staging: the tile's x rows (GRMSG: none), its aux rows (ADDLN residual / GRMS gate) and, for the
+// workgroup's first tile, gamma / beta, into the LDS image by DMA, 1 KiB pieces spread over the waves. Entry: no wave
+// still reads the image. Leaves: uncounted LDS-DMA loads in flight; the caller's next vmcnt wait, then a barrier.
+template <int K, int PRO, int NWV>
+__device__ __forceinline__ void stage_rows(const ZmiGemvArgs& a, const View<K>& L, int wave, int lane,
+                                           bool first, int s_row0, int s_rows) {
+  constexpr int XROW = Img<K>::XROW, GROW = Img<K>::GROW;
+  constexpr bool GRMS = Img<K>::grms(PRO), AUX = PRO == PRO_ADDLN || GRMS;
+  constexpr int GB = (PRO == PRO_LN || PRO == PRO_ADDLN) ? 2 : (GRMS ? 1 : 0);  // gamma / beta rows
+  constexpr int PPR = K / 512;
+  const int n_x = PRO == PRO_GRMSG ? 0 : s_rows * PPR;  // GRMSG: no y rows
+  constexpr int APR = GRMS ? 2 * PPR : PPR;  // aux pieces per row (f32 gate rows: twice the bytes)
+  const int n_a = AUX ? s_rows * APR : 0;
+  const int n_pc = n_x + n_a + (first ? GB * PPR : 0);
+  const bf16_t* s_X = reinterpret_cast<const bf16_t*>(a.X) + (size_t)s_row0 * a.ldx;
+  const bf16_t* XA = AUX ? reinterpret_cast<const bf16_t*>(a.aux) + (size_t)s_row0 * a.ld_aux * (GRMS ? 2 : 1)
+                         : nullptr;
+  for (int pc = wave; pc < n_pc; pc += NWV) {
+    if (pc < n_x) {
+      const int r = pc / PPR, p = pc - r * PPR;
+      dma_piece(s_X + (size_t)r * a.ldx + p * 512 + lane * 8, L.xs + r * XROW + p * 512);
+    } else if (pc < n_x + n_a) {
+      const int r = (pc - n_x) / APR, p = (pc - n_x) - r * APR;
+      if (GRMS)  // 1 KiB = 256 f32 of the gate (GRMSG: g) row
+        dma_piece(XA + ((size_t)r * a.ld_aux + p * 256) * 2 + lane * 8,
+                  reinterpret_cast<bf16_t*>(L.xg + r * GROW + p * 256));
+      else
+        dma_piece(XA + (size_t)r * a.ld_aux + p * 512 + lane * 8, L.xa + r * XROW + p * 512);
+    } else {
+      const int q = pc - n_x - n_a, which = q / PPR, p = q - which * PPR;
+      const bf16_t* src = reinterpret_cast<const bf16_t*>(which ? a.ln_b : a.ln_w);
+      dma_piece(src + p * 512 + lane * 8, (which ? L.bet : L.gam) + p * 512);
+    }
+  }
 }
 
+// (1b) Epilogue-operand staging: the epilogue inputs that need no other load (residual inputs, or the rows' positions
+// and cache rows) into registers of the group's epilogue wave `ew`. Leaves: counted loads, older than the weight stream.
+template <int EPI, int RT>
+__device__ __forceinline__ void stage_epilogue_operands(const ZmiGemvArgs& a, bool ew, int lane, int rows, int row0,
+                                                        int col0, uint32_t (&res_pre)[(8 * RT + 63) / 64], int& q_pos,
+                                                        int& q_kvr) {
+  constexpr int NE = (8 * RT + 63) / 64;
+#pragma unroll
+  for (int i = 0; i < NE; ++i) res_pre[i] = 0;
+  q_pos = -1, q_kvr = 0;
+  if (EPI == ZMI_EPI_RESIDUAL && ew) {
+#pragma unroll
+    for (int i = 0; i < NE; ++i) {
+      const int e = lane + 64 * i, r = e >> 3, n = col0 + (e & 7);
+      if (r < rows && n < a.n_valid)
+        res_pre[i] = reinterpret_cast<const bf16_t*>(a.out)[(size_t)(row0 + r) * a.ldo + n];
+    }
+  }
+  if (EPI == ZMI_EPI_QKV && ew && (lane >> 2) < rows) {
+    q_pos = a.row_pos[row0 + (lane >> 2)];
+    q_kvr = a.row_kv[row0 + (lane >> 2)];
+  }
+}
+
+// (1') FUSE 3 (zmi_attn_block's out_proj role): the activation rows are the attention output, gathered from the
+// units' output granules instead of staged by DMA. Layout as zmi_attnblk.hip passes it in QkvFuse: a unit = (row, kv
+// head), 256 {bf16 pair, tag} words per unit at og_off (4 heads x 128 dims = 512 columns of K: the attention block
+// checks hq = 4 hkv, hd = 128), 8 merge-workgroup flags per unit at of_off, tag = position + 1.
+// Entry: every wave (two barriers inside); the weight stream may be in flight; `qpos` is the segment-sum area. Leaves:
+// the rows in LDS (position < 0: zero rows), visible after the tile barrier. Returns the mask of rows with position >= 0.
+template <int K, int NWV>
+__device__ __forceinline__ unsigned gather_attention_rows(const ZmiGemvArgs& a, const QkvFuse& fz, bf16_t* xs, int* qpos,
+                                                          int rows, int row0, int tid) {
+  constexpr int XROW = Img<K>::XROW;
+  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  // the rows' positions (tags) in LDS first: every later check reads them without a dependent global load
+  if (tid < rows) qpos[tid] = fz.pos[row0 + tid];
+  __syncthreads();
+  unsigned act_rows = 0u;
+  for (int r = 0; r < rows; ++r) act_rows |= (qpos[r] >= 0 ? 1u : 0u) << r;
+  // wave 0 polls the merge workgroups' flags of the launch's units (rows whose position is < 0 run no attention and
+  // contribute zero rows), sleeping between sweeps, until ANY unit has a flag up: the merges finish within ~0.4 us of
+  // each other (64 cheap flags instead of 2048 granules while the attention runs; a granule published after a sweep
+  // is picked up by the next one). Waiting for every unit's flag measured C2 step 922 us, no flag wait 908, this form
+  // 902-904 (profiles/r06_oproj_flag_wait_ab.jsonl).
+  const int n_units = rows * fz.hkv;
+  if (wave == 0) {
+    for (unsigned spins = 0;; ++spins) {
+      bool ok = false;
+      for (int u0 = 0; u0 < n_units; u0 += 8) {  // lane = (unit u0 + lane / 8, merge workgroup lane % 8)
+        const int u = u0 + (lane >> 3), qp = u < n_units ? qpos[u / fz.hkv] : -1;
+        const bool up = qp < 0 || (uint32_t)(ld_wt64(fz.gran + (size_t)(row0 * fz.hkv + u) * fz.gran_stride + fz.of_off +
+                                                        (lane & 7)) >> 32) == (uint32_t)qp + 1u;
+        // any flag of the unit: OR over the 8 lanes of the unit (DPP within each 8-lane group)
+        float f = up ? 1.f : 0.f;
+        f = fmaxf(f, dpp_mov<DPP_XOR1>(f));
+        f = fmaxf(f, dpp_mov<DPP_XOR2>(f));
+        f = fmaxf(f, dpp_mov<DPP_HALF_MIRROR>(f));
+        ok = ok || (u < n_units && f > 0.f);
+      }
+      if (__any(ok)) break;
+      if (spins > (1u << 18)) {
+        if (lane == 0) __hip_atomic_store(fz.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        break;
+      }
+      __builtin_amdgcn_s_sleep(2);
+    }
+  }
+  ZMI_GSTAMP(7);
+  __syncthreads();
+  // every thread polls its own granules of the units' outputs (unit (r, kh), pair j: dims kh hq/hkv hd + 2 j, + 1 of
+  // row r) until each carries its row's tag, then writes them into the LDS rows. GPT granules per thread per batch
+  // (2 rows x 4 kv heads: one batch), every load of a sweep issued before the first check, s_sleep 1 between sweeps.
+  constexpr int GPT = 4;
+  for (int e0 = tid; e0 < n_units * 256; e0 += GPT * NWV * 64) {
+    uint64_t gv[GPT];
+    int gq[GPT];
+    unsigned need = 0;
+#pragma unroll
+    for (int i = 0; i < GPT; ++i) {
+      const int e = e0 + NWV * 64 * i;
+      gq[i] = e < n_units * 256 ? qpos[(e >> 8) / fz.hkv] : -1;
+      gv[i] = 0ull;
+      if (gq[i] >= 0) need |= 1u << i;
+    }
+    for (unsigned spins = 0; need; ++spins) {
+#pragma unroll
+      for (int i = 0; i < GPT; ++i)
+        if ((need >> i) & 1)
+          gv[i] = ld_wt64(fz.gran + (size_t)(row0 * fz.hkv + ((e0 + NWV * 64 * i) >> 8)) * fz.gran_stride + fz.og_off +
+                          ((e0 + NWV * 64 * i) & 255));
+#pragma unroll
+      for (int i = 0; i < GPT; ++i)
+        if (((need >> i) & 1) && (uint32_t)(gv[i] >> 32) == (uint32_t)gq[i] + 1u) need &= ~(1u << i);
+      if (!need) break;
+      if (spins > (1u << 18)) {
+        __hip_atomic_store(fz.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        break;
+      }
+      __builtin_amdgcn_s_sleep(1);
+    }
+#pragma unroll
+    for (int i = 0; i < GPT; ++i) {
+      const int e = e0 + NWV * 64 * i;
+      if (e < n_units * 256) {
+        const int u = e >> 8, j = e & 255, r = u / fz.hkv, kh = u - r * fz.hkv;
+        *reinterpret_cast<uint32_t*>(xs + r * XROW + kh * 512 + 2 * j) = gq[i] >= 0 ? (uint32_t)gv[i] : 0u;
+      }
+    }
+  }
+  return act_rows;
+}
+
+// (3) The normalisation prologues (zmi_common.h arithmetic): task (row, part) per wave, so the few rows of a decode
+// step use every wave; partial sums meet in the segment-sum area `part` (free until the MFMA chain); each pass re-reads
+// its chunks from LDS (no row copy in VGPRs: the weight slice in flight already holds 4 NL of them, and occupancy
+// decides whether every workgroup of a wide GEMV is resident at once). One wave per row with no barriers between the
+// passes measured slower: C2 step 1001 vs 973 us.
+// Entry: every wave, after the tile barrier. Each ends with a barrier: the normalised bf16 rows visible, `part` free.
+// The fp32 two-pass statistics of LayerNorm and (ADD) add+LayerNorm: part[r NQ + q] = the sum of part q of row r,
+// part[RT NQ + r NQ + q] = the sum of its squared deviations from the row mean; a chunk's sum is ln_chunk_sum of x or
+// addln_chunk_sum of x + aux. A workgroup barrier after each pass.
+template <int K, int RT, int NWV, bool ADD>
+__device__ __forceinline__ void ln_statistics(const ZmiGemvArgs& a, const View<K>& L, int rows, int wave, int lane) {
+  constexpr int XROW = Img<K>::XROW, NQ = ln_parts(K), CPQ = K / (512 * NQ);
+  float* part = L.red;
+  const int ntask = rows * NQ;
+  auto pass = [&](int task, float mean, bool sq) {
+    const int r = task / NQ, q = task - r * NQ;
+    const int off = r * XROW + q * (K / NQ) + lane * 8;
+    float t = 0.f;
+#pragma unroll
+    for (int i = 0; i < CPQ; ++i) {
+      const uint4 xv = *reinterpret_cast<const uint4*>(L.xs + off + 512 * i);
+      if constexpr (ADD)
+        t += addln_chunk_sum(xv, *reinterpret_cast<const uint4*>(L.xa + off + 512 * i), mean, sq);
+      else
+        t += ln_chunk_sum(xv, mean, sq);
+    }
+    return wave_sum(t);
+  };
+  for (int task = wave; task < ntask; task += NWV) {
+    const float v = pass(task, 0.f, false);
+    if (lane == 0) part[task] = v;
+  }
+  __syncthreads();
+#if defined(ZMI_LN_STAMP) && ZMI_LN_STAMP == 1  // diagnostic builds only (tools/build_attnblk_stamps.sh)
+  ZMI_GSTAMP(7);
+#endif
+  for (int task = wave; task < ntask; task += NWV) {
+    const float mean = ln_combine<NQ>(part + (task / NQ) * NQ) / (float)K;
+    const float v = pass(task, mean, true);
+    if (lane == 0) part[RT * NQ + task] = v;
+  }
+  __syncthreads();
+#if defined(ZMI_LN_STAMP) && ZMI_LN_STAMP == 2
+  ZMI_GSTAMP(7);
+#endif
+}
+
+// LayerNorm (nn.LayerNorm): x * rstd + nbias through ln_apply, in place
+template <int K, int RT, int NWV>
+__device__ __forceinline__ void prologue_layernorm(const ZmiGemvArgs& a, const View<K>& L, int rows, int wave, int lane) {
+  constexpr int XROW = Img<K>::XROW, NQ = ln_parts(K), CPQ = K / (512 * NQ);
+  ln_statistics<K, RT, NWV, false>(a, L, rows, wave, lane);  // L.red: the parts' sums, then their squared deviations
+  for (int task = wave; task < rows * NQ; task += NWV) {
+    const int r = task / NQ, q = task - r * NQ;
+    const float mean = ln_combine<NQ>(L.red + r * NQ) / (float)K;
+    const float rstd = 1.0f / sqrtf(ln_combine<NQ>(L.red + RT * NQ + r * NQ) / (float)K + a.eps), nbias = -mean * rstd;
+    bf16_t* xr = L.xs + r * XROW + q * (K / NQ);
+#pragma unroll
+    for (int i = 0; i < CPQ; ++i) {
+      const int c = q * (K / NQ) / 8 + lane + 64 * i;
+      const uint4 xv = *reinterpret_cast<const uint4*>(xr + (lane + 64 * i) * 8);
+      *reinterpret_cast<uint4*>(xr + (lane + 64 * i) * 8) = ln_apply(
+          xv, *reinterpret_cast<const uint4*>(L.gam + c * 8), *reinterpret_cast<const uint4*>(L.bet + c * 8), rstd, nbias);
+    }
+  }
+  __syncthreads();
+}
+
+// layer_norm_fn prenorm: s = x + residual (fp32), LayerNorm(s) with ((s - mean) rstd) w + b, in place over x; with
+// `wres` (the column block 0 workgroup of each row tile) bf16(s) also goes to res_out, the next block's residual
+template <int K, int RT, int NWV>
+__device__ __forceinline__ void prologue_add_layernorm(const ZmiGemvArgs& a, const View<K>& L, int rows,
+                                                       int row0, bool wres, int wave, int lane) {
+  constexpr int XROW = Img<K>::XROW, NQ = ln_parts(K), CPQ = K / (512 * NQ);
+  ln_statistics<K, RT, NWV, true>(a, L, rows, wave, lane);  // L.red: the parts' sums, then their squared deviations
+  for (int task = wave; task < rows * NQ; task += NWV) {
+    const int r = task / NQ, q = task - r * NQ;
+    const float mean = ln_combine<NQ>(L.red + r * NQ) / (float)K;
+    const float rstd = 1.0f / sqrtf(ln_combine<NQ>(L.red + RT * NQ + r * NQ) / (float)K + a.eps);
+    bf16_t* hr = L.xs + r * XROW + q * (K / NQ);
+    const bf16_t* rr = L.xa + r * XROW + q * (K / NQ);
+#pragma unroll
+    for (int i = 0; i < CPQ; ++i) {
+      const int c = q * (K / NQ) / 8 + lane + 64 * i;
+      const uint4 hv = *reinterpret_cast<const uint4*>(hr + (lane + 64 * i) * 8);
+      const uint4 rv = *reinterpret_cast<const uint4*>(rr + (lane + 64 * i) * 8);
+      const uint4 gw = *reinterpret_cast<const uint4*>(L.gam + c * 8), gbv = *reinterpret_cast<const uint4*>(L.bet + c * 8);
+      const uint32_t h[4] = {hv.x, hv.y, hv.z, hv.w}, rs[4] = {rv.x, rv.y, rv.z, rv.w};
+      const uint32_t uw[4] = {gw.x, gw.y, gw.z, gw.w}, ub[4] = {gbv.x, gbv.y, gbv.z, gbv.w};
+      uint32_t o[4], so[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float s0 = bf2f(h[j]) + bf2f(rs[j]), s1 = bf2f(h[j] >> 16) + bf2f(rs[j] >> 16);
+        const float y0 = ((s0 - mean) * rstd) * bf2f(uw[j]) + bf2f(ub[j]);
+        const float y1 = ((s1 - mean) * rstd) * bf2f(uw[j] >> 16) + bf2f(ub[j] >> 16);
+        o[j] = f2bf(y0) | (f2bf(y1) << 16);
+        so[j] = f2bf(s0) | (f2bf(s1) << 16);
+      }
+      *reinterpret_cast<uint4*>(hr + (lane + 64 * i) * 8) = uint4{o[0], o[1], o[2], o[3]};
+      if (wres)
+        reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(a.res_out) + (size_t)(row0 + r) * a.ld_aux)[c] =
+            uint4{so[0], so[1], so[2], so[3]};
+    }
+  }
+  __syncthreads();
+}
+
+// RMSNormGated (norm_before_gate=False): g = y (z sigmoid(z)), out = g rstd w into the x rows; g recomputed in the
+// apply pass (the same bits), sums of g^2 element by element as zmi_gated_rmsnorm (PRO_GRMSG: g read from the aux
+// rows). A wave takes its (row, part) tasks two at a time (the second clamped, its results dropped): two independent
+// dependent-add chains in one straight-line body instead of one after the other (the K = 4096 out_proj has 4 waves
+// for 2 rows x 4 parts). One workgroup barrier between the passes.
+template <int K, int RT, int NWV, int PRO>
+__device__ __forceinline__ void prologue_gated_rmsnorm(const ZmiGemvArgs& a, const View<K>& L, int rows,
+                                                       int wave, int lane) {
+  constexpr int XROW = Img<K>::XROW, GROW = Img<K>::GROW, NQ = ln_parts(K), CPQ = K / (512 * NQ);
+  float* part = L.red;
+  const int ntask = rows * NQ;
+  for (int task0 = wave; task0 < ntask; task0 += 2 * NWV) {
+    float t[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int task = min(task0 + u * NWV, ntask - 1);
+      const int r = task / NQ, q = task - r * NQ;
+      const bf16_t* yr = L.xs + r * XROW + q * (K / NQ);
+      const float* zr = L.xg + r * GROW + q * (K / NQ);
+      t[u] = 0.f;
+#pragma unroll
+      for (int i = 0; i < CPQ; ++i) {
+        uint32_t y[4] = {0u, 0u, 0u, 0u};
+        if constexpr (PRO == PRO_GRMS) {
+          const uint4 yv = *reinterpret_cast<const uint4*>(yr + (lane + 64 * i) * 8);
+          y[0] = yv.x; y[1] = yv.y; y[2] = yv.z; y[3] = yv.w;
+        }
+        float gz[8];
+        load_gate(zr + (lane + 64 * i) * 8, gz);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float g = PRO == PRO_GRMSG ? gz[e] : gate_elem(y, gz, e);
+          t[u] += g * g;
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u) t[u] = wave_sum(t[u]);
+    if (lane == 0) {
+      part[task0] = t[0];
+      if (task0 + NWV < ntask) part[task0 + NWV] = t[1];
+    }
+  }
+  __syncthreads();
+  for (int task0 = wave; task0 < ntask; task0 += 2 * NWV) {
+    uint4 res[2][CPQ];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int task = min(task0 + u * NWV, ntask - 1);
+      const int r = task / NQ, q = task - r * NQ;
+      const float rstd = 1.0f / sqrtf(ln_combine<NQ>(part + r * NQ) / (float)K + a.eps);
+      const bf16_t* yr = L.xs + r * XROW + q * (K / NQ);
+      const float* zr = L.xg + r * GROW + q * (K / NQ);
+#pragma unroll
+      for (int i = 0; i < CPQ; ++i) {
+        const int c = q * (K / NQ) / 8 + lane + 64 * i;
+        uint32_t y[4] = {0u, 0u, 0u, 0u};
+        if constexpr (PRO == PRO_GRMS) {
+          const uint4 yv = *reinterpret_cast<const uint4*>(yr + (lane + 64 * i) * 8);
+          y[0] = yv.x; y[1] = yv.y; y[2] = yv.z; y[3] = yv.w;
+        }
+        const uint4 gw = *reinterpret_cast<const uint4*>(L.gam + c * 8);
+        const uint32_t uw[4] = {gw.x, gw.y, gw.z, gw.w};
+        float gz[8];
+        load_gate(zr + (lane + 64 * i) * 8, gz);
+        auto gv = [&](int e) { return PRO == PRO_GRMSG ? gz[e] : gate_elem(y, gz, e); };
+        uint32_t o[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          o[j] = f2bf((gv(2 * j) * rstd) * bf2f(uw[j])) | (f2bf((gv(2 * j + 1) * rstd) * bf2f(uw[j] >> 16)) << 16);
+        res[u][i] = uint4{o[0], o[1], o[2], o[3]};
+      }
+    }
+    // stores after both tasks' reads: the clamped duplicate task reads what the real one overwrites
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int task = task0 + u * NWV;
+      if (task < ntask) {
+        const int r = task / NQ, q = task - r * NQ;
+        bf16_t* yr = L.xs + r * XROW + q * (K / NQ);
+#pragma unroll
+        for (int i = 0; i < CPQ; ++i) *reinterpret_cast<uint4*>(yr + (lane + 64 * i) * 8) = res[u][i];
+      }
+    }
+  }
+  __syncthreads();
+}
+
+// One workgroup of the GEMV: block b's column block over its row tiles. The phases above and the row arithmetic of
+// zmi_gemv_row.h in order; spelled out here is what decides the LDS-DMA waits: the order of issue, the barriers and the
+// s_waitcnt / sched_barrier placement. The DMA pieces are inline asm the compiler does not count: the explicit
+// vmcnt(NWL) is their only wait, so no load may move between the staging calls and it except the NWL weight loads.
 template <int G, int W, int NL, int RT, int PRO, int EPI, int NTW, int FUSE = 0, int FMT = ZMI_WFMT_BF16>
 __device__ __forceinline__ void gemv_body(const ZmiGemvArgs& a, int n_cb, int n_rt, int b, char* smem,
                                           const QkvFuse& fz, int rpw = 1) {
@@ -281,29 +620,16 @@ __device__ __forceinline__ void gemv_body(const ZmiGemvArgs& a, int n_cb, int n_
                               RT == 16),
                 "the gathered-input form is zmi_attn_block's out_proj role (one tile, plain, residual or store epilogue)");
 
-  // block -> (column block, group of rpw row tiles): the groups of one column block take ids 8 apart.
-  // A workgroup keeps its weight slice in registers and runs its row tiles one after the other, each
-  // with the arithmetic of a lone tile (a row's result does not depend on rpw or M).
-  const int idx = b >> 3;
-  const int n_rg = (n_rt + rpw - 1) / rpw;
-  const int cb = (idx / n_rg) * 8 + (b & 7), rg = idx - (idx / n_rg) * n_rg;
+  // A workgroup keeps its weight slice in registers and runs its rpw row tiles one after the other, each with the
+  // arithmetic of a lone tile (a row's result does not depend on rpw or M).
+  const auto [cb, rg] = block_pos(b, n_rt, rpw);
   if (cb >= n_cb) return;  // padding block: exits before any barrier
   ZMI_GSTAMP(0);
-  const int alloc_rows = a.M < RT ? a.M : RT;
   int rt = rg * rpw;
   const int rt_end = min(n_rt, rt + rpw);
   int row0 = rt * RT;
   int rows = min(RT, a.M - row0);
-  constexpr bool GRMS = PRO == PRO_GRMS || PRO == PRO_GRMSG;
-  constexpr bool AUX = PRO == PRO_ADDLN || GRMS;
-  constexpr int GB = (PRO == PRO_LN || PRO == PRO_ADDLN) ? 2 : (GRMS ? 1 : 0);  // gamma / beta rows
-  constexpr int GROW = Img<K>::GROW;
-  bf16_t* xs = reinterpret_cast<bf16_t*>(smem);
-  bf16_t* xa = xs + (size_t)alloc_rows * XROW;  // aux rows: ADDLN bf16 residual, GRMS f32 gate
-  float* xg = reinterpret_cast<float*>(xa);
-  bf16_t* gam = xa + (PRO == PRO_ADDLN ? (size_t)alloc_rows * XROW : (GRMS ? (size_t)alloc_rows * GROW * 2 : 0));
-  bf16_t* bet = gam + K;
-  float* red = reinterpret_cast<float*>(gam + (size_t)GB * K);
+  const View<K> L = Img<K>::carve(smem, a.M < RT ? a.M : RT, PRO);
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform: SGPR descriptors, no waterfalls
@@ -313,487 +639,82 @@ __device__ __forceinline__ void gemv_body(const ZmiGemvArgs& a, int n_cb, int n_
   const bool g_ok = g_raw < ngroups;
   const int g = g_ok ? g_raw : ngroups - 1;  // clamped: every wave joins the barriers
   const int col0 = g * 8;
-  const bf16_t* X = reinterpret_cast<const bf16_t*>(a.X) + (size_t)row0 * a.ldx;
-  // epilogue operands that need no other load (older than the weights: covered by the vmcnt below).
-  // The group's first wave runs the epilogue; its lane handles outputs e = lane + 64 i.
-  const bool ew = (wk == 0) && g_ok;
+  const bool ew = (wk == 0) && g_ok;  // the group's first wave runs the epilogue
   constexpr int NE = (8 * RT + 63) / 64;
   uint32_t res_pre[NE];
   int q_pos = -1, q_kvr = 0;
   unsigned act_rows = ~0u;  // FUSE 3: rows whose position is >= 0 (the others ran no attention: no residual store)
 
-  // (1) activation rows (+ LayerNorm gamma / beta, first tile only) into LDS by DMA, 1 KiB pieces
-  // spread over waves; then the tile's epilogue operands
-  // the DMA of a tile's rows (s_row0, s_rows, s_X) is split from its epilogue operands: in the multi-tile
-  // loop the next tile's rows are issued as soon as every wave's MFMA chain has left the LDS image, under
-  // the current tile's reduction and epilogue
-  auto stage_rows = [&](bool first, int s_row0, int s_rows, const bf16_t* s_X) {
-    constexpr int PPR = K / 512;
-    const int n_x = PRO == PRO_GRMSG ? 0 : s_rows * PPR;  // GRMSG: no y rows
-    constexpr int APR = GRMS ? 2 * PPR : PPR;  // aux pieces per row (f32 gate rows: twice the bytes)
-    const int n_a = AUX ? s_rows * APR : 0;
-    const int n_pc = n_x + n_a + (first ? GB * PPR : 0);
-    const bf16_t* XA = AUX ? reinterpret_cast<const bf16_t*>(a.aux) + (size_t)s_row0 * a.ld_aux * (GRMS ? 2 : 1)
-                           : nullptr;
-    for (int pc = wave; pc < n_pc; pc += NWV) {
-      if (pc < n_x) {
-        const int r = pc / PPR, p = pc - r * PPR;
-        dma_piece(s_X + (size_t)r * a.ldx + p * 512 + lane * 8, xs + r * XROW + p * 512);
-      } else if (pc < n_x + n_a) {
-        const int r = (pc - n_x) / APR, p = (pc - n_x) - r * APR;
-        if (GRMS)  // 1 KiB = 256 f32 of the gate (GRMSG: g) row
-          dma_piece(XA + ((size_t)r * a.ld_aux + p * 256) * 2 + lane * 8,
-                    reinterpret_cast<bf16_t*>(xg + r * GROW + p * 256));
-        else
-          dma_piece(XA + (size_t)r * a.ld_aux + p * 512 + lane * 8, xa + r * XROW + p * 512);
-      } else {
-        const int q = pc - n_x - n_a, which = q / PPR, p = q - which * PPR;
-        const bf16_t* src = reinterpret_cast<const bf16_t*>(which ? a.ln_b : a.ln_w);
-        dma_piece(src + p * 512 + lane * 8, (which ? bet : gam) + p * 512);
-      }
-    }
-  };
-  auto stage_epi = [&]() {
-#pragma unroll
-    for (int i = 0; i < NE; ++i) res_pre[i] = 0;
-    q_pos = -1;
-    q_kvr = 0;
-    if (EPI == ZMI_EPI_RESIDUAL && ew) {
-#pragma unroll
-      for (int i = 0; i < NE; ++i) {
-        const int e = lane + 64 * i, r = e >> 3, n = col0 + (e & 7);
-        if (r < rows && n < a.n_valid)
-          res_pre[i] = reinterpret_cast<const bf16_t*>(a.out)[(size_t)(row0 + r) * a.ldo + n];
-      }
-    }
-    if (EPI == ZMI_EPI_QKV && ew && (lane >> 2) < rows) {
-      q_pos = a.row_pos[row0 + (lane >> 2)];
-      q_kvr = a.row_kv[row0 + (lane >> 2)];
-    }
-  };
-  if (FUSE != 3) stage_rows(true, row0, rows, X);  // FUSE 3: the rows come from the attention's granules (below)
-  stage_epi();
-  // fp8: the group's 8 column exponents, one 8-byte load per epilogue lane, older than the weights like the
-  // epilogue operands
+  // (1) the first tile's rows (FUSE 3: gathered below) and epilogue operands (split: the tile loop issues the next
+  // tile's rows as soon as every chain has left the LDS image, under the current tile's reduction and epilogue)
+  if (FUSE != 3) stage_rows<K, PRO, NWV>(a, L, wave, lane, true, row0, rows);
+  stage_epilogue_operands<EPI, RT>(a, ew, lane, rows, row0, col0, res_pre, q_pos, q_kvr);
+  // fp8: the group's 8 column exponents, one 8-byte load per epilogue lane, older than the weights
   uint2 wexp = {0u, 0u};
   if constexpr (F8) {
     if (ew) wexp = *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(a.w_exp) + col0);
   }
   __builtin_amdgcn_sched_barrier(0);
-  // (2) the whole weight slice of this lane, in flight at once: one buffer descriptor per wave
-  // (wave-uniform base), lane offset in the VGPR, chunk offset j KiB folded into the instruction
-  // (cdna_hip_programming.md T8). Non-temporal when each weight is read once (one row tile).
-  // fp8: half the bytes, so NWL = NL / 2 loads of two chunks each.
-  const char* wbase = reinterpret_cast<const char*>(a.W) + ((size_t)g * KC + wk * NL) * CHB;
-  const __amdgpu_buffer_rsrc_t wrsrc =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(wbase), (short)0, NL * CHB, 0x00020000);
+  // (2) the lane's whole weight slice, in flight at once; non-temporal when each weight is read once (one row tile)
   u32x4_t wf[NWL];
-#pragma unroll
-  for (int j = 0; j < NWL; ++j) wf[j] = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, lane * 16, j * 1024, NTW ? 2 : 0);
+  load_weights_m8<NWL, NTW ? 2 : 0>(reinterpret_cast<const char*>(a.W) + ((size_t)g * KC + wk * NL) * CHB, NL * CHB,
+                                    lane, wf);
   __builtin_amdgcn_sched_barrier(0);
   ZMI_GSTAMP(1);
   // DMA pieces + epilogue operands landed: everything but this lane's NWL weight loads
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NWL) : "memory");
+  if constexpr (F8) {  // landed, and the same for every lane of the wave: kept in SGPRs through the prologue
+    wexp.x = __builtin_amdgcn_readfirstlane(wexp.x);
+    wexp.y = __builtin_amdgcn_readfirstlane(wexp.y);
+  }
   // single-tile QKV launches (every decode step): the epilogue's RoPE cos / sin pair, issued now that the row's
   // position has landed, so it arrives under the LayerNorm and the MFMA chain instead of after them
   float2 rope_cs = {1.f, 0.f};
   if (EPI == ZMI_EPI_QKV && NTW && ew && (lane >> 2) < rows && q_pos >= 0 && q_pos < a.smax) {
-    const int n = col0 + (lane & 3) * 2, qcols = a.hq * a.hd;
-    if (n < qcols + a.hkv * a.hd) {
-      const int d = (n < qcols ? n : n - qcols) % a.hd;
-      rope_cs = *reinterpret_cast<const float2*>(a.rope + ((size_t)q_pos * (a.hd >> 1) + (d >> 1)) * 2);
-    }
+    const int n = col0 + (lane & 3) * 2;
+    if (n < a.hq * a.hd + a.hkv * a.hd) rope_cs = *rope_pair(a, q_pos, n);
   }
   __builtin_amdgcn_sched_barrier(0);
-  if constexpr (FUSE == 3) {
-    // the rows' positions (tags) in LDS first: every later check reads them without a dependent global load
-    int* qpos = reinterpret_cast<int*>(red);  // the segment-sum area, free until the MFMA chain
-    if (tid < rows) qpos[tid] = fz.pos[row0 + tid];
-    __syncthreads();
-    act_rows = 0u;
-    for (int r = 0; r < rows; ++r) act_rows |= (qpos[r] >= 0 ? 1u : 0u) << r;
-    // (1') wave 0 polls the merge workgroups' flags of the launch's units (8 per (row, kv head); rows whose position
-    // is < 0 run no attention and contribute zero rows), sleeping between sweeps, until a unit has a flag up (below):
-    // the merges are then nearly done (64 cheap flags instead of 2048 granules while the attention runs)
-    const int n_units = rows * fz.hkv;
-#ifndef ZMI_OPROJ_FLAGS
-// how long wave 0 waits on the flags before every thread polls its granules: 1 = until ANY unit has a flag up (the
-// merges finish within ~0.4 us of each other; a granule published after the sweep is picked up by the next one), 0 =
-// until every unit has one (a flag round trip, then a granule round trip: C2 step 922 us against 902-904 with 1),
-// 2 = no wait (every thread polls from dispatch: 908) (profiles/r06_oproj_flag_wait_ab.jsonl)
-#define ZMI_OPROJ_FLAGS 1
-#endif
-#ifndef ZMI_OPROJ_SLEEP
-#define ZMI_OPROJ_SLEEP 1
-#endif
-    if (wave == 0 && ZMI_OPROJ_FLAGS != 2) {
-      for (unsigned spins = 0;; ++spins) {
-        bool ok = ZMI_OPROJ_FLAGS == 0;
-        for (int u0 = 0; u0 < n_units; u0 += 8) {  // lane = (unit u0 + lane / 8, merge workgroup lane % 8)
-          const int u = u0 + (lane >> 3), qp = u < n_units ? qpos[u / fz.hkv] : -1;
-          const bool up = qp < 0 || (uint32_t)(ld_wt64(fz.gran + (size_t)(row0 * fz.hkv + u) * fz.gran_stride + fz.of_off +
-                                                          (lane & 7)) >> 32) == (uint32_t)qp + 1u;
-          // any flag of the unit: OR over the 8 lanes of the unit (DPP within each 8-lane group)
-          float f = up ? 1.f : 0.f;
-          f = fmaxf(f, dpp_mov<DPP_XOR1>(f));
-          f = fmaxf(f, dpp_mov<DPP_XOR2>(f));
-          f = fmaxf(f, dpp_mov<DPP_HALF_MIRROR>(f));
-          if (ZMI_OPROJ_FLAGS == 0)
-            ok = ok && f > 0.f;
-          else
-            ok = ok || (u < n_units && f > 0.f);
-        }
-        if (ZMI_OPROJ_FLAGS == 0 ? __all(ok) : __any(ok)) break;
-        if (spins > (1u << 18)) {
-          if (lane == 0) __hip_atomic_store(fz.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          break;
-        }
-        __builtin_amdgcn_s_sleep(2);
-      }
-    }
-    ZMI_GSTAMP(7);
-    __syncthreads();
-    // (2') every thread polls its own {pair, tag} granules of the units' outputs (unit (r, kh), pair j: dims
-    // kh hq/hkv hd + 2 j, + 1 of row r; a unit's output is 4 heads x 128 dims = 512 columns of K: the attention block
-    // checks hq = 4 hkv, hd = 128) until each carries its row's tag, then writes them into the LDS rows. GB granules
-    // per thread per batch (2 rows x 4 kv heads: one batch), every load of a sweep issued before the first check.
-    constexpr int GB = 4;
-    for (int e0 = tid; e0 < n_units * 256; e0 += GB * NWV * 64) {
-      uint64_t gv[GB];
-      int gq[GB];
-      unsigned need = 0;
-#pragma unroll
-      for (int i = 0; i < GB; ++i) {
-        const int e = e0 + NWV * 64 * i;
-        gq[i] = e < n_units * 256 ? qpos[(e >> 8) / fz.hkv] : -1;
-        gv[i] = 0ull;
-        if (gq[i] >= 0) need |= 1u << i;
-      }
-      for (unsigned spins = 0; need; ++spins) {
-#pragma unroll
-        for (int i = 0; i < GB; ++i)
-          if ((need >> i) & 1)
-            gv[i] = ld_wt64(fz.gran + (size_t)(row0 * fz.hkv + ((e0 + NWV * 64 * i) >> 8)) * fz.gran_stride + fz.og_off +
-                            ((e0 + NWV * 64 * i) & 255));
-#pragma unroll
-        for (int i = 0; i < GB; ++i)
-          if (((need >> i) & 1) && (uint32_t)(gv[i] >> 32) == (uint32_t)gq[i] + 1u) need &= ~(1u << i);
-        if (!need) break;
-        if (spins > (1u << 18)) {
-          __hip_atomic_store(fz.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          break;
-        }
-        __builtin_amdgcn_s_sleep(ZMI_OPROJ_SLEEP);
-      }
-#pragma unroll
-      for (int i = 0; i < GB; ++i) {
-        const int e = e0 + NWV * 64 * i;
-        if (e < n_units * 256) {
-          const int u = e >> 8, j = e & 255, r = u / fz.hkv, kh = u - r * fz.hkv;
-          *reinterpret_cast<uint32_t*>(xs + r * XROW + kh * 512 + 2 * j) = gq[i] >= 0 ? (uint32_t)gv[i] : 0u;
-        }
-      }
-    }
-  }
+  if constexpr (FUSE == 3)  // (1') with its own two barriers; the segment-sum area holds the rows' positions meanwhile
+    act_rows = gather_attention_rows<K, NWV>(a, fz, L.xs, reinterpret_cast<int*>(L.red), rows, row0, tid);
   for (;;) {  // the workgroup's row tiles
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
-  ZMI_GSTAMP(2);
+    __builtin_amdgcn_s_barrier();  // the tile's rows (and gamma / beta) are visible to every wave
+    __builtin_amdgcn_sched_barrier(0);
+    ZMI_GSTAMP(2);
+    // (3) the prologue normalises the rows in place; each ends with a workgroup barrier
+    if constexpr (PRO == PRO_LN) prologue_layernorm<K, RT, NWV>(a, L, rows, wave, lane);
+    if constexpr (PRO == PRO_ADDLN)
+      prologue_add_layernorm<K, RT, NWV>(a, L, rows, row0, a.res_out != nullptr && cb == 0, wave, lane);
+    if constexpr (PRO == PRO_GRMS || PRO == PRO_GRMSG) prologue_gated_rmsnorm<K, RT, NWV, PRO>(a, L, rows, wave, lane);
+    ZMI_GSTAMP(3);
 
-  // (3) LayerNorm (zmi_common.h arithmetic): task (row, part) per wave, so the few rows of a decode
-  // step use every wave; partial sums meet in the segment-sum area (free until the MFMA chain).
-  // Each pass re-reads its chunks from LDS (no row copy in VGPRs: the weight slice in flight
-  // already holds 4 NL of them, and occupancy decides whether every workgroup of a wide GEMV is
-  // resident at once).
-#ifndef ZMI_LN_ROWWAVE  // (row, part) tasks spread over the waves, barriers between the passes; the A/B build
-                        // -DZMI_LN_ROWWAVE (one wave per row, no barriers) measured slower: C2 step 1001 vs 973 us
-  if (PRO == PRO_LN) {
-    constexpr int NQ = ln_parts(K), CPQ = K / (512 * NQ);
-    float* part = red;
-    const int ntask = rows * NQ;
-    auto pass = [&](int task, float mean, bool sq) {
-      const int r = task / NQ, q = task - r * NQ;
-      const bf16_t* xr = xs + r * XROW + q * (K / NQ);
-      float t = 0.f;
-#pragma unroll
-      for (int i = 0; i < CPQ; ++i) t += ln_chunk_sum(*reinterpret_cast<const uint4*>(xr + (lane + 64 * i) * 8), mean, sq);
-      return wave_sum(t);
-    };
-    for (int task = wave; task < ntask; task += NWV) {
-      const float v = pass(task, 0.f, false);
-      if (lane == 0) part[task] = v;
-    }
-    __syncthreads();
-#if defined(ZMI_LN_STAMP) && ZMI_LN_STAMP == 1  // diagnostic builds only (tools/build_attnblk_stamps.sh)
-    ZMI_GSTAMP(7);
-#endif
-    for (int task = wave; task < ntask; task += NWV) {
-      const float mean = ln_combine<NQ>(part + (task / NQ) * NQ) / (float)K;
-      const float v = pass(task, mean, true);
-      if (lane == 0) part[RT * NQ + task] = v;
-    }
-    __syncthreads();
-#if defined(ZMI_LN_STAMP) && ZMI_LN_STAMP == 2
-    ZMI_GSTAMP(7);
-#endif
-    for (int task = wave; task < ntask; task += NWV) {
-      const int r = task / NQ, q = task - r * NQ;
-      const float mean = ln_combine<NQ>(part + r * NQ) / (float)K;
-      const float rstd = 1.0f / sqrtf(ln_combine<NQ>(part + RT * NQ + r * NQ) / (float)K + a.eps), nbias = -mean * rstd;
-      bf16_t* xr = xs + r * XROW + q * (K / NQ);
-#pragma unroll
-      for (int i = 0; i < CPQ; ++i) {
-        const int c = q * (K / NQ) / 8 + lane + 64 * i;
-        const uint4 xv = *reinterpret_cast<const uint4*>(xr + (lane + 64 * i) * 8);
-        *reinterpret_cast<uint4*>(xr + (lane + 64 * i) * 8) = ln_apply(
-            xv, *reinterpret_cast<const uint4*>(gam + c * 8), *reinterpret_cast<const uint4*>(bet + c * 8), rstd, nbias);
-      }
-    }
-    __syncthreads();
-  }
-#else
-  if (PRO == PRO_LN) {
-    // one wave per row: the row's NQ part sums (each the wave_sum of its lanes' chunk sums, as
-    // zmi_layernorm_rows forms them) are all held by that wave, so the three passes need no workgroup
-    // barrier; the row's own LDS writes and reads are ordered within the wave
-    constexpr int NQ = ln_parts(K), CPQ = K / (512 * NQ);
-    for (int r = wave; r < rows; r += NWV) {
-      bf16_t* xr = xs + r * XROW;
-      auto pass = [&](float mean, bool sq, float(&ps)[NQ]) {
-        float tq[NQ];
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-          tq[q] = 0.f;
-#pragma unroll
-          for (int i = 0; i < CPQ; ++i)
-            tq[q] += ln_chunk_sum(*reinterpret_cast<const uint4*>(xr + q * (K / NQ) + (lane + 64 * i) * 8), mean, sq);
-        }
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) ps[q] = wave_sum(tq[q]);
-      };
-      float ps[NQ];
-      pass(0.f, false, ps);
-      const float mean = ln_combine<NQ>(ps) / (float)K;
-      pass(mean, true, ps);
-      const float rstd = 1.0f / sqrtf(ln_combine<NQ>(ps) / (float)K + a.eps), nbias = -mean * rstd;
-#pragma unroll
-      for (int q = 0; q < NQ; ++q)
-#pragma unroll
-        for (int i = 0; i < CPQ; ++i) {
-          const int c = q * (K / NQ) / 8 + lane + 64 * i;
-          bf16_t* xc = xr + q * (K / NQ) + (lane + 64 * i) * 8;
-          const uint4 xv = *reinterpret_cast<const uint4*>(xc);
-          *reinterpret_cast<uint4*>(xc) = ln_apply(xv, *reinterpret_cast<const uint4*>(gam + c * 8),
-                                                   *reinterpret_cast<const uint4*>(bet + c * 8), rstd, nbias);
-        }
-    }
-    __syncthreads();
-  }
-#endif
-  if (PRO == PRO_ADDLN) {
-    // layer_norm_fn prenorm: s = x + residual (fp32), LayerNorm(s) with (s - mean) rstd w + b; the column
-    // block 0 workgroup of each row tile writes bf16(s), the next block's residual
-    constexpr int NQ = ln_parts(K), CPQ = K / (512 * NQ);
-    float* part = red;
-    const int ntask = rows * NQ;
-    auto pass = [&](int task, float mean, bool sq) {
-      const int r = task / NQ, q = task - r * NQ;
-      const bf16_t* hr = xs + r * XROW + q * (K / NQ);
-      const bf16_t* rr = xa + r * XROW + q * (K / NQ);
-      float t = 0.f;
-#pragma unroll
-      for (int i = 0; i < CPQ; ++i)
-        t += addln_chunk_sum(*reinterpret_cast<const uint4*>(hr + (lane + 64 * i) * 8),
-                             *reinterpret_cast<const uint4*>(rr + (lane + 64 * i) * 8), mean, sq);
-      return wave_sum(t);
-    };
-    for (int task = wave; task < ntask; task += NWV) {
-      const float v = pass(task, 0.f, false);
-      if (lane == 0) part[task] = v;
-    }
-    __syncthreads();
-    for (int task = wave; task < ntask; task += NWV) {
-      const int r = task / NQ;
-      const float mean = ln_combine<NQ>(part + r * NQ) / (float)K;
-      const float v = pass(task, mean, true);
-      if (lane == 0) part[RT * NQ + task] = v;
-    }
-    __syncthreads();
-    const bool wres = a.res_out != nullptr && cb == 0;
-    for (int task = wave; task < ntask; task += NWV) {
-      const int r = task / NQ, q = task - r * NQ;
-      const float mean = ln_combine<NQ>(part + r * NQ) / (float)K;
-      const float rstd = 1.0f / sqrtf(ln_combine<NQ>(part + RT * NQ + r * NQ) / (float)K + a.eps);
-      bf16_t* hr = xs + r * XROW + q * (K / NQ);
-      const bf16_t* rr = xa + r * XROW + q * (K / NQ);
-#pragma unroll
-      for (int i = 0; i < CPQ; ++i) {
-        const int c = q * (K / NQ) / 8 + lane + 64 * i;
-        const uint4 hv = *reinterpret_cast<const uint4*>(hr + (lane + 64 * i) * 8);
-        const uint4 rv = *reinterpret_cast<const uint4*>(rr + (lane + 64 * i) * 8);
-        const uint4 gw = *reinterpret_cast<const uint4*>(gam + c * 8), gbv = *reinterpret_cast<const uint4*>(bet + c * 8);
-        const uint32_t h[4] = {hv.x, hv.y, hv.z, hv.w}, rs[4] = {rv.x, rv.y, rv.z, rv.w};
-        const uint32_t uw[4] = {gw.x, gw.y, gw.z, gw.w}, ub[4] = {gbv.x, gbv.y, gbv.z, gbv.w};
-        uint32_t o[4], so[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const float s0 = bf2f(h[j]) + bf2f(rs[j]), s1 = bf2f(h[j] >> 16) + bf2f(rs[j] >> 16);
-          const float y0 = ((s0 - mean) * rstd) * bf2f(uw[j]) + bf2f(ub[j]);
-          const float y1 = ((s1 - mean) * rstd) * bf2f(uw[j] >> 16) + bf2f(ub[j] >> 16);
-          o[j] = f2bf(y0) | (f2bf(y1) << 16);
-          so[j] = f2bf(s0) | (f2bf(s1) << 16);
-        }
-        *reinterpret_cast<uint4*>(hr + (lane + 64 * i) * 8) = uint4{o[0], o[1], o[2], o[3]};
-        if (wres)
-          reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(a.res_out) + (size_t)(row0 + r) * a.ld_aux)[c] =
-              uint4{so[0], so[1], so[2], so[3]};
-      }
-    }
-    __syncthreads();
-  }
-  if (GRMS) {
-    // RMSNormGated (norm_before_gate=False): g = y (z sigmoid(z)), out = g rstd w; g recomputed in the
-    // apply pass (the same bits), sums of g^2 element by element as zmi_gated_rmsnorm. A wave takes its
-    // (row, part) tasks two at a time (the second clamped, its results dropped): two independent dependent-add
-    // chains in one straight-line body instead of one after the other (the K = 4096 out_proj has 4 waves for
-    // 2 rows x 4 parts)
-    constexpr int NQ = ln_parts(K), CPQ = K / (512 * NQ);
-    float* part = red;
-    const int ntask = rows * NQ;
-    for (int task0 = wave; task0 < ntask; task0 += 2 * NWV) {
-      float t[2];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const int task = min(task0 + u * NWV, ntask - 1);
-        const int r = task / NQ, q = task - r * NQ;
-        const bf16_t* yr = xs + r * XROW + q * (K / NQ);
-        const float* zr = xg + r * GROW + q * (K / NQ);
-        t[u] = 0.f;
-#pragma unroll
-        for (int i = 0; i < CPQ; ++i) {
-          uint32_t y[4] = {0u, 0u, 0u, 0u};
-          if constexpr (PRO == PRO_GRMS) {
-            const uint4 yv = *reinterpret_cast<const uint4*>(yr + (lane + 64 * i) * 8);
-            y[0] = yv.x; y[1] = yv.y; y[2] = yv.z; y[3] = yv.w;
-          }
-          float gz[8];
-          load_gate(zr + (lane + 64 * i) * 8, gz);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const float g = PRO == PRO_GRMSG ? gz[e] : gate_elem(y, gz, e);
-            t[u] += g * g;
-          }
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < 2; ++u) t[u] = wave_sum(t[u]);
-      if (lane == 0) {
-        part[task0] = t[0];
-        if (task0 + NWV < ntask) part[task0 + NWV] = t[1];
-      }
-    }
-    __syncthreads();
-    for (int task0 = wave; task0 < ntask; task0 += 2 * NWV) {
-      uint4 res[2][CPQ];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const int task = min(task0 + u * NWV, ntask - 1);
-        const int r = task / NQ, q = task - r * NQ;
-        const float rstd = 1.0f / sqrtf(ln_combine<NQ>(part + r * NQ) / (float)K + a.eps);
-        const bf16_t* yr = xs + r * XROW + q * (K / NQ);
-        const float* zr = xg + r * GROW + q * (K / NQ);
-#pragma unroll
-        for (int i = 0; i < CPQ; ++i) {
-          const int c = q * (K / NQ) / 8 + lane + 64 * i;
-          uint32_t y[4] = {0u, 0u, 0u, 0u};
-          if constexpr (PRO == PRO_GRMS) {
-            const uint4 yv = *reinterpret_cast<const uint4*>(yr + (lane + 64 * i) * 8);
-            y[0] = yv.x; y[1] = yv.y; y[2] = yv.z; y[3] = yv.w;
-          }
-          const uint4 gw = *reinterpret_cast<const uint4*>(gam + c * 8);
-          const uint32_t uw[4] = {gw.x, gw.y, gw.z, gw.w};
-          float gz[8];
-          load_gate(zr + (lane + 64 * i) * 8, gz);
-          auto gv = [&](int e) { return PRO == PRO_GRMSG ? gz[e] : gate_elem(y, gz, e); };
-          uint32_t o[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            o[j] = f2bf((gv(2 * j) * rstd) * bf2f(uw[j])) | (f2bf((gv(2 * j + 1) * rstd) * bf2f(uw[j] >> 16)) << 16);
-          res[u][i] = uint4{o[0], o[1], o[2], o[3]};
-        }
-      }
-      // stores after both tasks' reads: the clamped duplicate task reads what the real one overwrites
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const int task = task0 + u * NWV;
-        if (task < ntask) {
-          const int r = task / NQ, q = task - r * NQ;
-          bf16_t* yr = xs + r * XROW + q * (K / NQ);
-#pragma unroll
-          for (int i = 0; i < CPQ; ++i) *reinterpret_cast<uint4*>(yr + (lane + 64 * i) * 8) = res[u][i];
-        }
-      }
-    }
-    __syncthreads();
-  }
-  ZMI_GSTAMP(3);
-
-  // (4) MFMA chain over this wave's k-segment. A operand: lane l reads row l & 15 (rows past the
-  // tile re-read its last row; those outputs are discarded), k = 8 (l >> 4) .. +7 of the k-half.
-  f32x4_t acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-  {
-    const int ar = min(lane & 15, rows - 1);
-    const bf16_t* xa = xs + ar * XROW + wk * NL * 64 + (lane >> 4) * 8;
-#pragma unroll
-    for (int j = 0; j < NL; ++j) {
-      const uint4 x0 = *reinterpret_cast<const uint4*>(xa + j * 64);
-      const uint4 x1 = *reinterpret_cast<const uint4*>(xa + j * 64 + 32);
-      bf16x8_t wv;
-      if constexpr (F8)  // the raw bytes stay in the registers; every row tile converts them again
-        wv = fp8x8_to_bf16x8(wf[j >> 1][2 * (j & 1)], wf[j >> 1][2 * (j & 1) + 1]);
-      else
-        wv = __builtin_bit_cast(bf16x8_t, wf[j]);
-      acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, x0), wv, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, x1), wv, acc1, 0, 0, 0);
-    }
-  }
-  ZMI_GSTAMP(4);
-  // (5) segment sum = k-half 0 (tile columns 0..7) + k-half 1 (tile columns 8..15, moved down by
-  // DPP); accumulator element q of lane l is row 4 (l >> 4) + q, column l & 15
-  {
-    const int c = lane & 15, rb = (lane >> 4) * 4;
+    // (4) MFMA chain over this wave's k-segment (rows past the tile re-read its last row). The weights' first use.
+    f32x4_t acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+    chain_m8<NL, F8>(L.xs + min(lane & 15, rows - 1) * XROW + wk * NL * 64 + (lane >> 4) * 8, wf, acc0, acc1);
+    ZMI_GSTAMP(4);
+    const SegPos sp = segment_pos<false>(lane);  // (5) the wave's segment sums into red[wave][column][row]
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const float v = acc0[q] + ror8(acc1[q]);
-      if (c < 8 && rb + q < RT) red[(wave * 8 + c) * RT + rb + q] = v;
+      const float v = segment_value<false>(acc0, acc1, q);
+      if (sp.live && sp.rb + q < RT) L.red[(wave * 8 + sp.c) * RT + sp.rb + q] = v;
     }
-  }
-  __syncthreads();
-  ZMI_GSTAMP(5);
-  if (!NTW && rt + 1 < rt_end) {  // every chain is done with the LDS image: the next tile's rows go in now
-    const int n_row0 = (rt + 1) * RT;
-    stage_rows(false, n_row0, min(RT, a.M - n_row0), reinterpret_cast<const bf16_t*>(a.X) + (size_t)n_row0 * a.ldx);
-  }
-  if (ew) {
-    auto colsum = [&](int c, int r) {  // the group's W segment sums, in wave order
-      float v = red[((gi * W) * 8 + c) * RT + r];
-#pragma unroll
-      for (int w = 1; w < W; ++w) v += red[((gi * W + w) * 8 + c) * RT + r];
-      if constexpr (F8) v *= fp8_col_scale(wexp, c);  // exact: a power of two
-      return v;
-    };
-    epilogue<EPI, RT, FUSE>(a, colsum, lane, rows, row0, g, res_pre, q_pos, q_kvr, fz, act_rows,
-                            (EPI == ZMI_EPI_QKV && NTW) ? &rope_cs : nullptr);  // (6)
-  }
-  ZMI_GSTAMP(6);
-  // one tile when each weight is read once (NTW: M <= RT, every decode launch): no loop state there
-  if (NTW || ++rt >= rt_end) break;
-  __syncthreads();  // every wave is done with this tile's LDS image and segment sums
-  row0 = rt * RT;
-  rows = min(RT, a.M - row0);
-  X = reinterpret_cast<const bf16_t*>(a.X) + (size_t)row0 * a.ldx;
-  stage_epi();
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this tile's rows (the weights landed long ago)
+    __syncthreads();
+    ZMI_GSTAMP(5);
+    if (!NTW && rt + 1 < rt_end) {  // every chain is done with the LDS image: the next tile's rows go in now
+      const int n_row0 = (rt + 1) * RT;
+      stage_rows<K, PRO, NWV>(a, L, wave, lane, false, n_row0, min(RT, a.M - n_row0));
+    }
+    if (ew)  // (6) the group's W segment sums in wave order, then the fused epilogue
+      epilogue<EPI, RT, FUSE>(a, ColSum<W, RT, F8>{L.red + gi * W * 8 * RT, wexp}, lane, rows, row0, g, res_pre, q_pos,
+                              q_kvr, fz, act_rows, (EPI == ZMI_EPI_QKV && NTW) ? &rope_cs : nullptr);
+    ZMI_GSTAMP(6);
+    // one tile when each weight is read once (NTW: M <= RT, every decode launch): no loop state there
+    if (NTW || ++rt >= rt_end) break;
+    __syncthreads();  // every wave is done with this tile's LDS image and segment sums
+    row0 = rt * RT;
+    rows = min(RT, a.M - row0);
+    stage_epilogue_operands<EPI, RT>(a, ew, lane, rows, row0, col0, res_pre, q_pos, q_kvr);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this tile's rows (the weights landed long ago)
   }  // row tiles
 }
 
@@ -824,7 +745,8 @@ constexpr auto gemv_fn() {  // the kernel of a weight format (only the one asked
 
 // Many-row form of the K = 2048 GEMV (multi-slot decode and prefill, M > 16), the same per-row arithmetic as
 // gemv_body's (W, NL, RT) = (4, 8, 16) shape: a wave's chain of MFMAs over one k-segment (k-half 0 / 1 in
-// two accumulators, acc0 + ror8(acc1)), then the 4 segment sums in segment order, then epilogue().
+// two accumulators, their segment_value), then the 4 segment sums in segment order, then epilogue(): the row arithmetic
+// of zmi_gemv_row.h.
 // What changes is the reuse and the pipelining:
 //  * a workgroup owns 8 groups (64 columns) and each wave GPW of them over one segment (GPW x 32 weight
 //    VGPRs), so every activation tile it stages serves 64 columns (gemv_body's 4-group form: 32, twice the
@@ -852,12 +774,7 @@ __device__ __forceinline__ void dma_dword(const void* gsrc, void* ldp) {
                : "memory");
 }
 
-//  * DN (dense pairs): each wave owns one PAIR of groups (16 columns) and feeds the MFMA a 16-column B operand per
-//    k-half: lane l = column l & 15 of the pair, k = 64 kc + 32 h + 8 (l >> 4) .. + 7, gathered from the two groups'
-//    M8 chunks at load time (lane (l & 7) + 8 h + 16 (l >> 4) of group 2p + ((l >> 3) & 1)). acc0 then holds every
-//    column's k-half-0 chain and acc1 its k-half-1 chain, the same products in the same MFMA accumulations as the M8
-//    form's columns 0..7 / 8..15 (a column's MFMA result does not depend on the column's place in the tile), and
-//    acc0 + acc1 is the M8 form's acc0 + ror8(acc1) for all 16 lanes: half the MFMAs of the M8 form, same bits.
+//  * DN (dense pairs, zmi_gemv_row.h): each wave owns one PAIR of groups; half the MFMAs of the M8 form, same bits.
 template <int EPI, int GPW, bool DN = false>
 __global__ __launch_bounds__(GR_G * 4 / GPW * 64 / (DN ? 2 : 1)) void gemm_rows_kernel(const ZmiGemvArgs a, int n_cb,
                                                                                        int n_rt, int rpw) {
@@ -877,9 +794,8 @@ __global__ __launch_bounds__(GR_G * 4 / GPW * 64 / (DN ? 2 : 1)) void gemm_rows_
   float* red = reinterpret_cast<float*>(smem + GR_RED);          // [group][segment][8][RT] segment sums
   char* ops = smem + GR_OPS;                                     // [2][2 KiB]
   unsigned* cnt = reinterpret_cast<unsigned*>(smem + GR_CNT);    // epilogues finished
-  const int b = blockIdx.x, idx = b >> 3;
-  const int n_rg = (n_rt + rpw - 1) / rpw;
-  const int cb = (idx / n_rg) * 8 + (b & 7), rg = idx - (idx / n_rg) * n_rg;  // gemv_body's XCD-aware map
+  const BlockPos bp = block_pos(blockIdx.x, n_rt, rpw);
+  const int cb = bp.cb, rg = bp.rg;
   if (cb >= n_cb) return;
   ZMI_GSTAMP(0);
   const int tid = threadIdx.x, lane = tid & 63;
@@ -930,33 +846,20 @@ __global__ __launch_bounds__(GR_G * 4 / GPW * 64 / (DN ? 2 : 1)) void gemm_rows_
   dma_tile(t0);
   if (t0 + 1 < rt_end) dma_tile(t0 + 1);
   __builtin_amdgcn_sched_barrier(0);
-  // the weight slices of the wave's groups (GPW NL x 16 B per lane), in flight at once, in chain order (chunk
-  // j of every group before chunk j + 1): the first tile's chains follow them as they land. Re-read by the
-  // other row groups of this column block from L2 (temporal).
+  // the weight slices of the wave's groups (GPW NL x 16 B per lane), in flight at once (all waited for below, before
+  // the first chain). Re-read by the other row groups of this column block from L2 (temporal).
   u32x4_t wf[DN ? 2 : GPW][NL];  // DN: wf[h][j] = k-half h of chunk j for the wave's pair
   if constexpr (DN) {
-    // lane l: column l & 15 of pair gs (group cb * 8 + 2 gs + ((l >> 3) & 1), clamped: discarded), M8 lane
-    // (l & 7) + 8 h + 16 (l >> 4) of that group's chunk
-    const int grp = min(cb * GR_G + 2 * gs + ((lane >> 3) & 1), ngroups - 1) - cb * GR_G;
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<char*>(reinterpret_cast<const char*>(a.W) + (size_t)cb * GR_G * KC * 1024), (short)0,
-        GR_G * KC * 1024, 0x00020000);
-    const int vo = (grp * KC + wk * NL) * 1024 + ((lane & 7) + 16 * (lane >> 4)) * 16;
-#pragma unroll
-    for (int j = 0; j < NL; ++j)
-#pragma unroll
-      for (int h = 0; h < 2; ++h) wf[h][j] = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, vo + 128 * h, j * 1024, 0);
+    // lane l: column l & 15 of pair gs (group cb * 8 + 2 gs + dn_member(l), clamped: discarded); the descriptor
+    // spans the column block's 8 groups
+    const int grp = min(cb * GR_G + 2 * gs + dn_member(lane), ngroups - 1) - cb * GR_G;
+    load_weights_dn<NL, 0>(reinterpret_cast<const char*>(a.W) + (size_t)cb * GR_G * KC * 1024, GR_G * KC * 1024,
+                           (grp * KC + wk * NL) * 1024, lane, wf);
   } else {
-    __amdgpu_buffer_rsrc_t wrsrc[GPW];
 #pragma unroll
     for (int h = 0; h < GPW; ++h)
-      wrsrc[h] = __builtin_amdgcn_make_buffer_rsrc(
-          const_cast<char*>(reinterpret_cast<const char*>(a.W) + ((size_t)gg[h] * KC + wk * NL) * 1024), (short)0,
-          NL * 1024, 0x00020000);
-#pragma unroll
-    for (int j = 0; j < NL; ++j)
-#pragma unroll
-      for (int h = 0; h < GPW; ++h) wf[h][j] = __builtin_amdgcn_raw_buffer_load_b128(wrsrc[h], lane * 16, j * 1024, 0);
+      load_weights_m8<NL, 0>(reinterpret_cast<const char*>(a.W) + ((size_t)gg[h] * KC + wk * NL) * 1024, NL * 1024, lane,
+                             wf[h]);
   }
   __builtin_amdgcn_sched_barrier(0);
   // every weight slice and the first two tiles' pieces: waiting here for all of them keeps the compiler's own
@@ -973,23 +876,13 @@ __global__ __launch_bounds__(GR_G * 4 / GPW * 64 / (DN ? 2 : 1)) void gemm_rows_
     f32x4_t acc0[GPW], acc1[GPW];
 #pragma unroll
     for (int h = 0; h < GPW; ++h) acc0[h] = acc1[h] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    {
+    {  // the chains of the wave's groups over the same A fragments (every row of the tile is staged: no clamp)
       const bf16_t* xa = xs + (t & 1) * RT * XROW + (lane & 15) * XROW + wk * NL * 64 + (lane >> 4) * 8;
+      if constexpr (DN) {
+        chain_dn<NL>(xa, wf, acc0[0], acc1[0]);
+      } else {
 #pragma unroll
-      for (int j = 0; j < NL; ++j) {
-        const bf16x8_t x0 = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(xa + j * 64));
-        const bf16x8_t x1 = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(xa + j * 64 + 32));
-        if constexpr (DN) {
-          acc0[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x0, __builtin_bit_cast(bf16x8_t, wf[0][j]), acc0[0], 0, 0, 0);
-          acc1[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x1, __builtin_bit_cast(bf16x8_t, wf[1][j]), acc1[0], 0, 0, 0);
-        } else {
-#pragma unroll
-          for (int h = 0; h < GPW; ++h) {
-            const bf16x8_t wv = __builtin_bit_cast(bf16x8_t, wf[h][j]);
-            acc0[h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x0, wv, acc0[h], 0, 0, 0);
-            acc1[h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x1, wv, acc1[h], 0, 0, 0);
-          }
-        }
+        for (int h = 0; h < GPW; ++h) chain_m8<NL, false>(xa, wf[h], acc0[h], acc1[h]);
       }
     }
     if (ti == 0) ZMI_GSTAMP(1);
@@ -1000,21 +893,16 @@ __global__ __launch_bounds__(GR_G * 4 / GPW * 64 / (DN ? 2 : 1)) void gemm_rows_
       for (int spin = 0; *lcnt < want && spin < (1 << 20); ++spin)
         __builtin_amdgcn_s_sleep(1);
     }
-    {
-      const int c = lane & 15, rb = (lane >> 4) * 4;
-      if constexpr (DN) {
+    {  // the segment sums into red[group][segment][column][row] (DN: the lane's own group of the pair)
+      const SegPos sp = segment_pos<DN>(lane);
 #pragma unroll
-        for (int q = 0; q < 4; ++q)
-          red[(((2 * gs + (c >> 3)) * W + wk) * 8 + (c & 7)) * RT + rb + q] = acc0[0][q] + acc1[0][q];
-      } else {
+      for (int h = 0; h < (DN ? 1 : GPW); ++h)
 #pragma unroll
-        for (int h = 0; h < GPW; ++h)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const float v = acc0[h][q] + ror8(acc1[h][q]);
-            if (c < 8) red[(((gs + NGS * h) * W + wk) * 8 + c) * RT + rb + q] = v;
-          }
-      }
+        for (int q = 0; q < 4; ++q) {
+          const float v = segment_value<DN>(acc0[h], acc1[h], q);
+          const int grp = DN ? 2 * gs + (sp.c >> 3) : gs + NGS * h;
+          if (sp.live) red[((grp * W + wk) * 8 + (sp.c & 7)) * RT + sp.rb + q] = v;
+        }
     }
     // this tile's epilogue operands into registers before the buffer is re-filled
     uint32_t res_pre[NE] = {0u, 0u};
@@ -1041,14 +929,9 @@ __global__ __launch_bounds__(GR_G * 4 / GPW * 64 / (DN ? 2 : 1)) void gemm_rows_
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
     if (ti == 1) ZMI_GSTAMP(4);
     if (t + 2 < rt_end) dma_tile(t + 2);
-    if (ew) {
-      auto colsum = [&](int c, int r) {  // segment sums in segment order (gemv_body's wave order)
-        float v = red[((wave * W) * 8 + c) * RT + r];
-#pragma unroll
-        for (int w = 1; w < W; ++w) v += red[((wave * W + w) * 8 + c) * RT + r];
-        return v;
-      };
-      epilogue<EPI, RT, 0>(a, colsum, lane, rows, row0, eg, res_pre, q_pos, q_kvr, QkvFuse{nullptr, 0});
+    if (ew) {  // group cb * 8 + wave: its segment sums in segment order (gemv_body's wave order)
+      epilogue<EPI, RT, 0>(a, ColSum<W, RT>{red + wave * W * 8 * RT}, lane, rows, row0, eg, res_pre, q_pos, q_kvr,
+                           QkvFuse{nullptr, 0});
       if (more && lane == 0) __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
     if (ti == 1) ZMI_GSTAMP(5);
@@ -1076,7 +959,7 @@ inline int rows_per_wg(int n_cb, int n_rt, int target) {
 struct Shape {
   int W, NL, RT;
 };
-inline bool shape_for(int K, bool ln, Shape* s) {
+inline bool shape_for(int K, Shape* s) {
   switch (K) {
     case 512: *s = {2, 4, 16}; return true;
     case 1024: *s = {4, 4, 16}; return true;
@@ -1113,7 +996,7 @@ hipError_t launch_p(const ZmiGemvArgs& a, hipStream_t s) {
   size_t lds = Img<K>::bytes(a.M < RT ? a.M : RT, G * W, RT, PRO);
   if (lds > LDS_MAX) return hipErrorInvalidValue;
   const int rpw = rows_per_wg(n_cb, n_rt, K == 8192 ? 256 : 512);
-  const int64_t blocks = (int64_t)((n_cb + 7) / 8) * 8 * ((n_rt + rpw - 1) / rpw);
+  const int64_t blocks = block_count(n_cb, n_rt, rpw);
   if (NTW && zmi_option(ZMI_OPT_GEMV_SPREAD)) {
     // a decode launch streams each weight once: its rate is the number of CUs it keeps busy (one CU
     // pulls ~25 GB/s), so reserve LDS such that at most ceil(blocks / CUs) workgroups share a CU
@@ -1134,38 +1017,30 @@ hipError_t launch_p(const ZmiGemvArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
-// fp8 weights (ZMI_WFMT_FP8): LayerNorm'd or plain rows, one tile (non-temporal) or the row-tile loop
-template <int G, int W, int NL, int RT, int EPI>
-hipError_t launch_g8(const ZmiGemvArgs& a, hipStream_t s) {
-  constexpr int F = ZMI_WFMT_FP8;
-  const bool once = a.M <= RT;
-  if (a.ln_w != nullptr)
-    return once ? launch_p<G, W, NL, RT, PRO_LN, EPI, 1, F>(a, s) : launch_p<G, W, NL, RT, PRO_LN, EPI, 0, F>(a, s);
-  return once ? launch_p<G, W, NL, RT, PRO_PLAIN, EPI, 1, F>(a, s) : launch_p<G, W, NL, RT, PRO_PLAIN, EPI, 0, F>(a, s);
+// one row tile (M <= RT: each weight is read once, the non-temporal single-tile instantiation) or the row-tile loop
+template <int G, int W, int NL, int RT, int PRO, int EPI, int FMT = ZMI_WFMT_BF16>
+hipError_t launch_tiles(const ZmiGemvArgs& a, hipStream_t s) {
+  return a.M <= RT ? launch_p<G, W, NL, RT, PRO, EPI, 1, FMT>(a, s) : launch_p<G, W, NL, RT, PRO, EPI, 0, FMT>(a, s);
 }
 
-template <int G, int W, int NL, int RT, int EPI>
+// the prologue of a shape, where it is built: fp8 weights for LayerNorm'd or plain rows and not for K = 4096 (no fp8
+// projection has it); ADDLN (the hybrid blocks' d_model GEMVs) for K 512 / 2048; GRMS (the Mamba2 out_proj, K = d_ssm)
+// for K 1024 / 4096 with the store epilogue, GRMS_G (the same from g = y * gate rows) on one tile (decode)
+template <int G, int W, int NL, int RT, int EPI, int FMT>
 hipError_t launch_g(const ZmiGemvArgs& a, hipStream_t s) {
   constexpr int K = W * NL * 64;
-  const bool ln = a.ln_w != nullptr;
-  const bool once = a.M <= RT;  // each weight read once: non-temporal loads
-  if (a.pro == ZMI_PRO_ADDLN) {  // the hybrid blocks' d_model GEMVs
-    if constexpr ((K == 512 || K == 2048) && EPI != ZMI_EPI_RESIDUAL && EPI != ZMI_EPI_F32)
-      return once ? launch_p<G, W, NL, RT, PRO_ADDLN, EPI, 1>(a, s) : launch_p<G, W, NL, RT, PRO_ADDLN, EPI, 0>(a, s);
-    return hipErrorInvalidValue;
+  constexpr bool F8 = FMT == ZMI_WFMT_FP8;
+  if constexpr (!F8 && (K == 512 || K == 2048) && EPI != ZMI_EPI_RESIDUAL && EPI != ZMI_EPI_F32)
+    if (a.pro == ZMI_PRO_ADDLN) return launch_tiles<G, W, NL, RT, PRO_ADDLN, EPI>(a, s);
+  if constexpr (!F8 && (K == 1024 || K == 4096) && EPI == ZMI_EPI_STORE) {
+    if (a.pro == ZMI_PRO_GRMS) return launch_tiles<G, W, NL, RT, PRO_GRMS, EPI>(a, s);
+    if (a.pro == ZMI_PRO_GRMS_G && a.M <= RT) return launch_p<G, W, NL, RT, PRO_GRMSG, EPI, 1>(a, s);
   }
-  if (a.pro == ZMI_PRO_GRMS) {  // the Mamba2 out_proj (K = d_ssm)
-    if constexpr ((K == 1024 || K == 4096) && EPI == ZMI_EPI_STORE)
-      return once ? launch_p<G, W, NL, RT, PRO_GRMS, EPI, 1>(a, s) : launch_p<G, W, NL, RT, PRO_GRMS, EPI, 0>(a, s);
-    return hipErrorInvalidValue;
+  if constexpr (!F8 || K != 4096) {
+    if (a.pro == ZMI_PRO_AUTO && a.ln_w != nullptr) return launch_tiles<G, W, NL, RT, PRO_LN, EPI, FMT>(a, s);
+    if (a.pro == ZMI_PRO_AUTO) return launch_tiles<G, W, NL, RT, PRO_PLAIN, EPI, FMT>(a, s);
   }
-  if (a.pro == ZMI_PRO_GRMS_G) {  // the same from g = y * gate rows (decode: one tile)
-    if constexpr ((K == 1024 || K == 4096) && EPI == ZMI_EPI_STORE)
-      return once ? launch_p<G, W, NL, RT, PRO_GRMSG, EPI, 1>(a, s) : hipErrorInvalidValue;
-    return hipErrorInvalidValue;
-  }
-  if (ln) return once ? launch_p<G, W, NL, RT, PRO_LN, EPI, 1>(a, s) : launch_p<G, W, NL, RT, PRO_LN, EPI, 0>(a, s);
-  return once ? launch_p<G, W, NL, RT, PRO_PLAIN, EPI, 1>(a, s) : launch_p<G, W, NL, RT, PRO_PLAIN, EPI, 0>(a, s);
+  return hipErrorInvalidValue;
 }
 
 // where the many-row form beats gemv_body's 4-group tile loop (C3 decode shapes, tools/kernel_bench.py
@@ -1180,7 +1055,7 @@ hipError_t launch_rows(const ZmiGemvArgs& a, hipStream_t s) {
   const int n_cb = (a.N / 8 + GR_G - 1) / GR_G;
   const int n_rt = (a.M + GR_RT - 1) / GR_RT;
   const int rpw = rows_per_wg(n_cb, n_rt, zmi_cu_count());  // one workgroup per CU
-  const int64_t blocks = (int64_t)((n_cb + 7) / 8) * 8 * ((n_rt + rpw - 1) / rpw);
+  const int64_t blocks = block_count(n_cb, n_rt, rpw);
   static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(fn),
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX);
   if (attr != hipSuccess) return attr;
@@ -1189,37 +1064,13 @@ hipError_t launch_rows(const ZmiGemvArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
-template <int EPI>
-hipError_t launch(const ZmiGemvArgs& a, hipStream_t s) {
-  Shape sh;
-  if (!shape_for(a.K, a.ln_w != nullptr, &sh)) return hipErrorInvalidValue;
-  const int g = groups_for(a, sh);
-  if (a.w_fmt == ZMI_WFMT_FP8) {
-    // fp8 weights run gemv_body's tile loop for every M: the many-row form below (and the split-K GEMM) read bf16
-    // weights only. All forms agree bit for bit, so this costs many-row speed, never bits.
-    if constexpr (EPI == ZMI_EPI_SWIGLU || EPI == ZMI_EPI_RESIDUAL || EPI == ZMI_EPI_F32) {
-      if (a.pro != ZMI_PRO_AUTO) return hipErrorInvalidValue;
-      if (g == 4 && sh.W == 4 && sh.NL == 8 && sh.RT == 16 && a.M > sh.RT && a.ln_w == nullptr)
-        return launch_p<4, 4, 8, 16, PRO_PLAIN, EPI, 0, ZMI_WFMT_FP8>(a, s);
-#define ZMI_SHAPE8(G_, W_, NL_, RT_) \
-  if (g == G_ && sh.W == W_ && sh.NL == NL_ && sh.RT == RT_) return launch_g8<G_, W_, NL_, RT_, EPI>(a, s);
-      ZMI_SHAPE8(1, 2, 4, 16)
-      ZMI_SHAPE8(1, 4, 4, 16)
-      ZMI_SHAPE8(1, 4, 8, 16)
-      ZMI_SHAPE8(2, 4, 8, 16)
-      ZMI_SHAPE8(1, 8, 16, 8)
-      ZMI_SHAPE8(2, 8, 16, 8)
-#undef ZMI_SHAPE8
-    }
-    return hipErrorInvalidValue;
-  }
-  if (a.K == 2048 && a.M > GR_RT && a.ln_w == nullptr && a.pro == ZMI_PRO_AUTO && a.groups == 0 &&
-      zmi_option(ZMI_OPT_GEMM_ROWS) && rows_form(a.M, a.N))
-    return (zmi_option(ZMI_OPT_GEMM_ROWS) & 2) ? launch_rows<EPI, 1, true>(a, s) : launch_rows<EPI, 2, false>(a, s);
+// gemv_body's launches of one weight format: the (G, W, NL, RT) instantiations that are built
+template <int EPI, int FMT>
+hipError_t launch_shape(const ZmiGemvArgs& a, hipStream_t s, const Shape& sh, int g) {
   if (g == 4 && sh.W == 4 && sh.NL == 8 && sh.RT == 16 && a.M > sh.RT && a.ln_w == nullptr && a.pro == ZMI_PRO_AUTO)
-    return launch_p<4, 4, 8, 16, PRO_PLAIN, EPI, 0>(a, s);  // groups_for's many-row plain case only
+    return launch_p<4, 4, 8, 16, PRO_PLAIN, EPI, 0, FMT>(a, s);  // groups_for's many-row plain case only
 #define ZMI_SHAPE(G_, W_, NL_, RT_) \
-  if (g == G_ && sh.W == W_ && sh.NL == NL_ && sh.RT == RT_) return launch_g<G_, W_, NL_, RT_, EPI>(a, s);
+  if (g == G_ && sh.W == W_ && sh.NL == NL_ && sh.RT == RT_) return launch_g<G_, W_, NL_, RT_, EPI, FMT>(a, s);
   ZMI_SHAPE(1, 2, 4, 16)
   ZMI_SHAPE(1, 4, 4, 16)
   ZMI_SHAPE(1, 4, 8, 16)
@@ -1229,6 +1080,24 @@ hipError_t launch(const ZmiGemvArgs& a, hipStream_t s) {
   ZMI_SHAPE(2, 8, 16, 8)
 #undef ZMI_SHAPE
   return hipErrorInvalidValue;  // e.g. groups = 2 outside the LayerNorm'd K = 2048 shape
+}
+
+template <int EPI>
+hipError_t launch(const ZmiGemvArgs& a, hipStream_t s) {
+  Shape sh;
+  if (!shape_for(a.K, &sh)) return hipErrorInvalidValue;
+  const int g = groups_for(a, sh);
+  if (a.w_fmt == ZMI_WFMT_FP8) {
+    // fp8 weights run gemv_body's tile loop for every M: the many-row form below (and the split-K GEMM) read bf16
+    // weights only. All forms agree bit for bit, so this costs many-row speed, never bits.
+    if constexpr (EPI == ZMI_EPI_SWIGLU || EPI == ZMI_EPI_RESIDUAL || EPI == ZMI_EPI_F32)
+      return launch_shape<EPI, ZMI_WFMT_FP8>(a, s, sh, g);
+    return hipErrorInvalidValue;
+  }
+  if (a.K == 2048 && a.M > GR_RT && a.ln_w == nullptr && a.pro == ZMI_PRO_AUTO && a.groups == 0 &&
+      zmi_option(ZMI_OPT_GEMM_ROWS) && rows_form(a.M, a.N))
+    return (zmi_option(ZMI_OPT_GEMM_ROWS) & 2) ? launch_rows<EPI, 1, true>(a, s) : launch_rows<EPI, 2, false>(a, s);
+  return launch_shape<EPI, ZMI_WFMT_BF16>(a, s, sh, g);
 }
 
 }  // namespace zmi_gemv
