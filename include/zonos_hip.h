@@ -312,6 +312,19 @@ int zmi_dac_conv_out_range_lanes(const void* x, int t, int c_in, const void* w_p
                                  int n, float* out, int lanes, int64_t ls_x, int64_t ls_out, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * PCM16 egress (the reference server's float -> 16-bit PCM conversion, server.py:142-146:
+ *   wav_numpy = np.clip(wav_numpy, -1.0, 1.0); wav_int16 = (wav_numpy * 32767).astype(np.int16)
+ * which numpy evaluates in fp32 and truncates), for many waveform pieces in one launch.
+ * ------------------------------------------------------------------------------------- */
+typedef struct ZmiPcmSeg { const float* src; int64_t n; int64_t dst; } ZmiPcmSeg;  /* n samples -> out[dst .. dst + n) */
+/* out[dst + j] = (int16) trunc(fl32(clamp(src[j], -1, 1) * 32767.0f)) for every segment: truncation toward zero,
+ * +-inf -> +-32767, -0.0 and subnormals -> 0, NaN -> 0. segs: DEVICE array of n_segs segments, dst ascending and
+ * non-overlapping (n may be 0); total = the last dst + n. src needs 4-byte alignment only and dst is any int16 index
+ * (out 2-byte aligned): a segment's ends go elementwise, its aligned middle in 8-byte stores. Nothing outside the
+ * segments' ranges is written; n_segs = 0 or total = 0 launches nothing. */
+int zmi_pcm16_pack(const ZmiPcmSeg* segs, int n_segs, int64_t total, int16_t* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Speaker encoder (Zonos.make_speaker_embedding, model.py:90-95 -> SpeakerEmbeddingLDA, speaker_cloning.py:388-412:
  * ResNet293 with SimAM blocks). Activations are fp16 channels-last [H][W][C] (H the mel axis, W time, batch 1);
  * conv weights fp16 channel-blocked per tap [tap = ky k + kx][Ci/32][Co][32]; fp32 accumulation on MFMA. Every

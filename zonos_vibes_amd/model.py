@@ -5,6 +5,7 @@
     wav = model.autoencoder.decode(codes)                                # [1, 1, 512 T] fp32
     for wav in model.stream(prefix_conditioning): ...                    # the same samples, in chunks, as they are ready
     for i, wav, last in model.stream_batch(conds): ...                   # many utterances' chunks, each as decode(generate_batch)
+    with model.serve(64, 2048, 512, pcm16=True) as session: ...          # requests admitted mid-stream (serving.py)
 
 `generate` keeps the reference's arguments and batch_size=1 semantics; `generate_batch`
 runs many independent utterances through the slots of one engine (continuous batching at
@@ -22,6 +23,7 @@ from .autoencoder import DACAutoencoder
 from .conditioning import PrefixConditioner
 from .config import N_CODEBOOKS, ZonosConfig
 from .engine import ST_FIELDS, SamplingParams, codes_count, make_engine
+from .serving import BatchRounds, ServeSession
 
 
 def _draw_seed() -> int:
@@ -55,6 +57,7 @@ class Zonos:
         # time the overlapped form.
         self._stream_overlap = False
         self._stream_glue = None
+        self._serving = None  # the open serve() session, if any: it owns the slots
 
     @property
     def device(self) -> torch.device:
@@ -144,6 +147,7 @@ class Zonos:
         """Reference model.py:218-315 (batch_size=1). `disable_torch_compile` is accepted and ignored:
         the decode step is a hipGraph of hand-written kernels in every mode."""
         assert cfg_scale != 1, "TODO: add support for cfg_scale=1"
+        self._check_not_serving("generate")
         if batch_size != 1 or prefix_conditioning.shape[0] != 2:
             raise ValueError("the reference generate() supports batch_size=1 only (SURVEY.md §0.3); "
                              "use generate_batch() for many utterances")
@@ -202,6 +206,7 @@ class Zonos:
         all enqueued one round ahead of the host and ordered by events; the host waits only for a round's one small
         state copy before it yields the round's audio."""
         assert cfg_scale != 1, "TODO: add support for cfg_scale=1"
+        self._check_not_serving("stream")
         if prefix_conditioning.shape[0] != 2:
             raise ValueError("stream() has generate()'s batch_size=1 semantics: prefix_conditioning [2, Lc, d]")
         if chunk_frames < 1:
@@ -295,6 +300,7 @@ class Zonos:
                        sampling_params: dict = dict(min_p=0.1), seeds: Sequence[int] | None = None,
                        max_slots: int | None = None, chunk: int = 32) -> list[torch.Tensor]:
         """Many independent utterances through the engine's slots; result i equals generate() on utterance i."""
+        self._check_not_serving("generate_batch")
         n = len(conds)
         prefixes = list(prefixes) if prefixes is not None else [None] * n
         mnt = [max_new_tokens] * n if isinstance(max_new_tokens, int) else list(max_new_tokens)
@@ -364,6 +370,7 @@ class Zonos:
         DESIGN.md §5g): they are ordered behind the round's reads and the next round's steps wait for the
         autoencoder's stream. The state is read before the push, so nothing is decoded past an utterance's end."""
         assert cfg_scale != 1, "TODO: add support for cfg_scale=1"
+        self._check_not_serving("stream_batch")
         if chunk_frames < 1:
             raise ValueError("chunk_frames >= 1")
         n = len(conds)
@@ -386,11 +393,7 @@ class Zonos:
             dec.reset(s)  # (an earlier stream_batch closed before its end)
         queue = sorted(range(n), key=lambda i: -mnt[i])  # longest-processing-time first, so the tail is short
         owner = [-1] * slots
-        remaining, steps, read_to = [0] * slots, [0] * slots, [0] * slots
-        sizes = sorted({slots} | {b for b in (1, 2, 4, 8, 16, 24, 32, 40, 48, 56) if b < slots})
-        nf, S = len(ST_FIELDS), e.st_all.shape[1]
-        host = torch.empty(e.snapshot_all_ints(), dtype=torch.int32).pin_memory()
-        cur = torch.cuda.current_stream(self._device)
+        rounds = BatchRounds(e, ae, dec, slots, chunk_frames)  # the round serve() runs too (serving.py)
 
         def fill():
             items = []
@@ -400,56 +403,16 @@ class Zonos:
                     params = SamplingParams.from_dict(dict(sampling_params), cfg_scale, seeds[i])
                     items.append((s, conds[i], prefixes[i], mnt[i], params))
                     owner[s] = i
-                    remaining[s], steps[s], read_to[s] = mnt[i] + 8, 0, 0
+                    rounds.start(s, plen[i], mnt[i])
             e.prefill_many(items)
 
         try:
             fill()
             while any(o >= 0 for o in owner):
-                k = min(chunk_frames, max(r for s, r in enumerate(remaining) if owner[s] >= 0))
-                hi = max(s for s in range(slots) if owner[s] >= 0) + 1 if e.batch_shrink else slots
-                e.stream.wait_stream(ae.stream)  # the previous round's windows first
-                e.step(k, slots=next(b for b in sizes if b >= hi))
-                e.snapshot_all(host).synchronize()
-                vals = host.tolist()
-                if any(vals[nf * S:]):  # the words check_errors() reads, copied with the state
-                    e.check_errors()
-                pieces, ended = {}, []
-                for s in range(slots):
-                    if owner[s] < 0:
-                        continue
-                    i = owner[s]
-                    remaining[s] -= k
-                    steps[s] += k
-                    stt = {f: vals[j * S + s] for j, f in enumerate(ST_FIELDS)}
-                    if stt["active"]:
-                        t1 = min(plen[i] + 1 + steps[s] - 9, plen[i] + mnt[i])
-                        if t1 > read_to[s] and stt["offset"] - 9 < t1:
-                            raise RuntimeError("stream_batch: a slot's offset is behind the steps enqueued")
-                    else:  # ended (EOS countdown or max_new_tokens): read_codes' count
-                        t1 = codes_count(stt)
-                        ended.append(s)
-                    t1 = max(t1, read_to[s])
-                    if t1 > read_to[s]:
-                        pieces[s] = e.read_final_codes(s, read_to[s], t1)
-                        read_to[s] = t1
-                with torch.cuda.stream(e.stream):  # ordered behind the reads; the next round waits for ae.stream
-                    wavs = dec.push(pieces) if pieces else {}
-                    tails = dec.flush(ended) if ended else {}
-                    for s, tail in tails.items():
-                        w = wavs.get(s)
-                        wavs[s] = tail if w is None or w.shape[-1] == 0 else \
-                            w if tail.shape[-1] == 0 else torch.cat([w, tail], dim=-1)
-                cur.wait_stream(e.stream)
-                out = []
-                for s in sorted(wavs):
-                    last = s in tails
-                    if wavs[s].shape[-1] or last:
-                        wavs[s].record_stream(cur)
-                        out.append((owner[s], wavs[s], last))
+                wavs, ended = rounds.round([s for s in range(slots) if owner[s] >= 0])
+                out = [(owner[s], w, s in ended) for s, w in wavs.items()]
                 for s in ended:
                     owner[s] = -1
-                    e.pos_hi[s] = 0  # its rows are inactive (position -1): no bound on the attention form
                 fill()  # before the round's audio is handed out: the consumer's time is not the engine's
                 yield from out
         finally:
@@ -457,6 +420,21 @@ class Zonos:
                 dec.reset(s)
                 if owner[s] >= 0:
                     e.release(s)
+
+    def serve(self, max_slots: int, max_seqlen: int, max_prefill: int, chunk_frames: int = 16,
+              pcm16: bool = False) -> ServeSession:
+        """A serving session (serving.ServeSession, a context manager): submit() requests from any thread while
+        others are being spoken, run_round() from one thread hands out every ticket's chunks, each ticket's
+        concatenated bit for bit decode(generate_batch()) of the request alone; with pcm16 they leave as int16 CPU
+        tensors (zmi_pcm16_pack). Capacity is fixed here; while the session is open generate(), stream(),
+        generate_batch(), stream_batch() and another serve() raise RuntimeError."""
+        self._check_not_serving("serve")
+        return ServeSession(self, max_slots, max_seqlen, max_prefill, chunk_frames, pcm16)
+
+    def _check_not_serving(self, what: str):
+        if self._serving is not None:
+            raise RuntimeError(f"{what}(): a serve() session is open on this model (it owns the engine's slots); "
+                               "close it first")
 
     def __repr__(self):
         bb = self.config.backbone
