@@ -316,7 +316,9 @@ __global__ __launch_bounds__(SORT_THREADS) void sample_kernel(const SampleArgs a
         q = a.noise[((size_t)blockIdx.y * ZMI_NCB + cb) * NV + v];
       } else {
         const uint64_t z = mix64(P.seed + 0x9E3779B97F4A7C15ull * (ctr_base + v + 1));
-        const float u = ((float)(z >> 40) + 0.5f) * (1.0f / 16777216.0f);
+        // 16777215 + 0.5 rounds up to 2^24: u would be 1 and q = -0 (p / q = -inf, or NaN where p = 0, which the
+        // argmax neither takes nor replaces); clamped to the largest float below 1, every other draw's bits unchanged
+        const float u = fminf(((float)(z >> 40) + 0.5f) * (1.0f / 16777216.0f), 0x1.fffffep-1f);
         q = -logf(u);
       }
       const float r = probs[v] / q;
