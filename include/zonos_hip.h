@@ -325,6 +325,37 @@ typedef struct ZmiPcmSeg { const float* src; int64_t n; int64_t dst; } ZmiPcmSeg
 int zmi_pcm16_pack(const ZmiPcmSeg* segs, int n_segs, int64_t total, int16_t* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Sample-rate conversion orig_rate -> new_rate (the reference's torchaudio.functional.resample with its defaults,
+ * autoencoder.py:17-20): g = gcd, o = orig_rate / g, n = new_rate / g, W the table's half width and T = 2 W + o
+ * (speaker.resample_kernel(o, n)). For an utterance x[0 .. N), output j < ceil(n N / o) is
+ *   y[j] = sum_{t < T} xz[(j / n) o - W + t] * kern[j % n][t],   xz = x inside [0, N), 0 outside,
+ * in fp32: four accumulators a0..a3 from +0, tap t (ascending) into a[t & 3] by one fused multiply-add, result
+ * (a0 + a1) + (a2 + a3); the order depends on t alone, never on the lane, the launch shape or the chunking.
+ * One launch converts many independent pieces, each a stretch of one utterance's outputs:
+ * ------------------------------------------------------------------------------------- */
+typedef struct ZmiResampleSeg {
+  const float* carry; int64_t n_carry;   /* the lane's kept tail: the utterance's samples i0 .. i0 + n_carry          */
+  const float* src;   int64_t n_src;     /* new samples: i0 + n_carry .. i0 + n_carry + n_src                         */
+  int64_t i0, n_total;                   /* n_total: the utterance's length if this piece ends it, else -1            */
+  int64_t j0, n_out, dst;                /* the utterance's outputs j0 .. j0 + n_out -> out[dst .. dst + n_out)       */
+  float* carry_out;   int64_t n_keep;    /* zmi_resample_carry: the last n_keep samples of (carry, src) go here       */
+} ZmiResampleSeg;
+/* Samples below 0, at or above n_total (when >= 0) and outside [i0, i0 + n_carry + n_src) read as 0. segs: DEVICE
+ * array of n_segs segments, dst ascending and non-overlapping inside total_out (n_out may be 0); segs_host: the HOST
+ * copy of the same table, checked before anything is launched (counts, pointers, dst order, that every tap of a piece
+ * that is not final lies in its carry or src, that a final piece ends at n_total and emits no more than
+ * ceil(n n_total / o)): a bad table or a NULL pointer returns non-zero and nothing is written. kern_t: DEVICE
+ * [T][n] fp32, the table transposed (phases contiguous). n (2 W + o) <= 2^22. Nothing outside the segments' output
+ * ranges is written; n_segs = 0 or total_out = 0 launches nothing. */
+int zmi_resample(const ZmiResampleSeg* segs, const ZmiResampleSeg* segs_host, int n_segs, int64_t total_out,
+                 const float* kern_t, int o, int n, int W, float* out, void* stream);
+/* carry_out[0 .. n_keep) = the last n_keep (<= n_carry + n_src, <= T) samples of (carry, src) for every segment:
+ * the tail a streaming lane keeps for its next piece. carry_out is never the carry it is made from (the caller
+ * double-buffers), so this launch and zmi_resample on the same table may run in either order. */
+int zmi_resample_carry(const ZmiResampleSeg* segs, const ZmiResampleSeg* segs_host, int n_segs, int o, int n, int W,
+                       void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Speaker encoder (Zonos.make_speaker_embedding, model.py:90-95 -> SpeakerEmbeddingLDA, speaker_cloning.py:388-412:
  * ResNet293 with SimAM blocks). Activations are fp16 channels-last [H][W][C] (H the mel axis, W time, batch 1);
  * conv weights fp16 channel-blocked per tap [tap = ky k + kx][Ci/32][Co][32]; fp32 accumulation on MFMA. Every

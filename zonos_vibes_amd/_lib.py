@@ -149,6 +149,8 @@ _SIGS = {
     "zmi_dac_conv_out_range_lanes": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
                                              c_int64, c_int64, c_void_p]),
     "zmi_pcm16_pack": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p]),
+    "zmi_resample": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "zmi_resample_carry": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "zmi_dac_im2col7":(c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     "zmi_dac_vq": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                            c_void_p, c_void_p]),

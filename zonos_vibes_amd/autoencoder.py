@@ -19,6 +19,7 @@ import torch
 from . import _lib
 from . import synthetic as syn
 from .config import DAC_HOP, DAC_SAMPLE_RATE, N_CODEBOOKS
+from .resampling import GpuResampler, StreamResampler, resample_plan
 from .streaming import (DAC_LOOKAHEAD_FRAMES, DACBatchStreamDecoder, DACStreamDecoder,  # noqa: F401
                         dac_lookahead_frames)
 
@@ -240,6 +241,7 @@ class DACAutoencoder:
         self.lib = _lib.lib()
         self.stream = torch.cuda.Stream(self.dev)
         self.sptr = self.stream.cuda_stream
+        self._resamplers: dict = {}  # (o, n) -> GpuResampler (its table stays on the device)
         if state_dict is None:
             state_dict = {}
             with torch.cuda.stream(self.stream):
@@ -473,12 +475,45 @@ class DACAutoencoder:
 
     # --------------------------------------------------------------- encode
     def preprocess(self, wav: torch.Tensor, sr: int) -> torch.Tensor:
-        """autoencoder.py:17-20: resample to 44.1 kHz (identity only: torchaudio is absent) and right-pad to
-        a multiple of 512 samples."""
+        """autoencoder.py:17-20: resample to 44.1 kHz (zmi_resample: fp32 cuda tensors only, the kernel is the only
+        implementation; a CPU tensor raises NotImplementedError, another dtype ValueError) and right-pad to a multiple
+        of 512 samples. sr == 44100 only pads, whatever the device and dtype."""
         if sr != DAC_SAMPLE_RATE:
-            raise NotImplementedError(f"resampling {sr} Hz -> 44.1 kHz needs torchaudio (absent in this build)")
+            if not wav.is_cuda:
+                raise NotImplementedError(f"resampling {sr} Hz -> 44.1 kHz runs on the GPU only: pass a cuda tensor")
+            wav = self.resample(wav, sr, DAC_SAMPLE_RATE)
         right = math.ceil(wav.shape[-1] / DAC_HOP) * DAC_HOP - wav.shape[-1]
         return torch.nn.functional.pad(wav, (0, right))
+
+    @torch.inference_mode()
+    def resample(self, wav: torch.Tensor, orig_rate: int, new_rate: int) -> torch.Tensor:
+        """[..., N] fp32 cuda -> [..., ceil(new_rate N / orig_rate)]: torchaudio.functional.resample's defaults, every
+        leading row a segment of one zmi_resample launch on the autoencoder's stream (resampling.py). Equal rates
+        return the input; a CPU tensor raises NotImplementedError and a dtype other than fp32 ValueError (nothing is
+        cast silently)."""
+        key = resample_plan(orig_rate, new_rate)[:2]
+        if key[0] == key[1]:
+            return wav
+        if not wav.is_cuda:
+            raise NotImplementedError("resample() runs on the GPU only: pass a cuda tensor")
+        if wav.dtype != torch.float32:  # (no silent cast: the 44.1 kHz path of preprocess() keeps the input's dtype)
+            raise ValueError(f"resample() takes fp32 audio, got {wav.dtype}")
+        rs = self._resamplers.get(key)
+        if rs is None:
+            rs = self._resamplers[key] = GpuResampler(self.dev, *key)
+        cur = torch.cuda.current_stream(self.dev)
+        self.stream.wait_stream(cur)
+        with torch.cuda.stream(self.stream):
+            out = rs(wav.to(self.dev))
+        cur.wait_stream(self.stream)
+        out.record_stream(cur)
+        return out
+
+    def resampler(self, new_rate: int, lanes: int = 1) -> StreamResampler:
+        """`lanes` streaming resamplers from 44.1 kHz to new_rate (resampling.StreamResampler): push({lane: chunk},
+        final=...) / flush(lanes) / reset(lane); per lane the concatenated returns are bit for bit
+        resample(the whole waveform, 44100, new_rate). Its launches go to the stream that is current at each call."""
+        return StreamResampler(lanes, DAC_SAMPLE_RATE, new_rate, device=self.dev)
 
     def _encoder_buffers(self, n: int):
         need = 64 * (n + 8)

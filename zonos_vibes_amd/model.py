@@ -50,6 +50,7 @@ class Zonos:
         self.spk_clone_model = None      # created lazily (model.py:90-93) by make_speaker_embedding
         self._spk_synthetic_seed = None  # Zonos.synthetic: the seed of the synthetic speaker encoder
         self._stream_decoders: dict = {}  # stream(): one DACStreamDecoder per chunk_frames
+        self._stream_resamplers: dict = {}  # stream() / stream_batch(sample_rate=): one StreamResampler per rate
         self._stream_batch_decoders: dict = {}  # stream_batch(): one DACBatchStreamDecoder per chunk_frames
         # stream(): True lets the DAC windows run beside the next decode steps. Measured: the decode
         # step's codes are then not reproducible (a few utterances in ten diverge from generate() at some frame), so
@@ -195,7 +196,7 @@ class Zonos:
     @torch.inference_mode()
     def stream(self, prefix_conditioning: torch.Tensor, audio_prefix_codes: torch.Tensor | None = None,
                max_new_tokens: int = 86 * 30, cfg_scale: float = 2.0, sampling_params: dict = dict(min_p=0.1),
-               chunk_frames: int = 16):
+               chunk_frames: int = 16, sample_rate: int | None = None):
         """generate() + autoencoder.decode() as a generator of waveform chunks [1, 1, 512 n] fp32 (device): audio
         is yielded while the utterance is still being generated. With the same torch.manual_seed, the chunks
         concatenated are bit for bit decode(generate(...)) (batch 1, generate()'s arguments).
@@ -204,9 +205,15 @@ class Zonos:
         lookahead (DAC_LOOKAHEAD_FRAMES) beyond it is final too. A round is `chunk_frames` decode steps on the engine's
         stream, the read of the frames they make final, and those frames' DAC windows on the autoencoder's stream,
         all enqueued one round ahead of the host and ordered by events; the host waits only for a round's one small
-        state copy before it yields the round's audio."""
+        state copy before it yields the round's audio.
+
+        sample_rate (None or 44100: exactly the path above): the chunks leave at that rate, [1, 1, any n > 0], and
+        concatenated are bit for bit autoencoder.resample(decode(generate(...)), 44100, sample_rate). A round's
+        waveform goes through a streaming resampler (resampling.StreamResampler, zmi_resample) once the round's state
+        copy has shown how much of it counts, so the resampler is never rolled back."""
         assert cfg_scale != 1, "TODO: add support for cfg_scale=1"
         self._check_not_serving("stream")
+        rate = self._output_rate(sample_rate)
         if prefix_conditioning.shape[0] != 2:
             raise ValueError("stream() has generate()'s batch_size=1 semantics: prefix_conditioning [2, Lc, d]")
         if chunk_frames < 1:
@@ -222,6 +229,7 @@ class Zonos:
             self._stream_decoders[key] = self.autoencoder.stream_decoder(chunk_frames)
         dec = self._stream_decoders[key]
         dec._reset()  # (an earlier stream closed before its end)
+        rs = None if rate is None else self._stream_resampler(rate, 1)
         n_audio, max_steps = p + max_new_tokens, max_new_tokens + 8
         host = [torch.empty(e.SNAPSHOT_INTS, dtype=torch.int32).pin_memory() for _ in range(2)]
         cur = torch.cuda.current_stream(self._device)
@@ -286,12 +294,19 @@ class Zonos:
                         wav = tail if wav.shape[-1] == 0 else torch.cat([wav, tail], dim=-1)
                         ready = torch.cuda.Event()
                         ready.record(glue)
+                if rs is not None and (wav.shape[-1] or not stt["active"]):  # fed only what is known to count
+                    with torch.cuda.stream(glue):
+                        wav = rs.push({0: wav}, final=() if stt["active"] else (0,))[0]
+                        ready = torch.cuda.Event()
+                        ready.record(glue)
                 if wav.shape[-1]:
                     cur.wait_event(ready)
                     wav.record_stream(cur)
                     yield wav
         finally:
             dec._reset()
+            if rs is not None:
+                rs.reset(0)
             e.release(slot)
 
     @torch.inference_mode()
@@ -355,7 +370,7 @@ class Zonos:
     def stream_batch(self, conds: Sequence[torch.Tensor], prefixes: Sequence[torch.Tensor | None] | None = None,
                      max_new_tokens: Sequence[int] | int = 86 * 30, cfg_scale: float = 2.0,
                      sampling_params: dict = dict(min_p=0.1), seeds: Sequence[int] | None = None,
-                     max_slots: int | None = None, chunk_frames: int = 16):
+                     max_slots: int | None = None, chunk_frames: int = 16, sample_rate: int | None = None):
         """generate_batch() + autoencoder.decode() per utterance as a generator of (utterance index, waveform chunk
         [1, 1, 512 n] fp32 (device), last): every utterance's audio is yielded while it and the others are still being
         generated. With the same seeds, utterance i's chunks concatenated are bit for bit
@@ -368,9 +383,14 @@ class Zonos:
         of equal shape as lanes of one launch sequence. Slots that ended are flushed and refilled from the queue
         (longest first). The DAC windows run between the rounds, never beside decode steps (stream()'s ordering rule,
         DESIGN.md §5g): they are ordered behind the round's reads and the next round's steps wait for the
-        autoencoder's stream. The state is read before the push, so nothing is decoded past an utterance's end."""
+        autoencoder's stream. The state is read before the push, so nothing is decoded past an utterance's end.
+
+        sample_rate (None or 44100: exactly the path above): a round's waveforms go through ONE push of a streaming
+        resampler over the slots (zmi_resample, on the engine's stream); utterance i's chunks, [1, 1, any n >= 0],
+        concatenated are bit for bit autoencoder.resample(decode(generate_batch(...)[i]), 44100, sample_rate)."""
         assert cfg_scale != 1, "TODO: add support for cfg_scale=1"
         self._check_not_serving("stream_batch")
+        rate = self._output_rate(sample_rate)
         if chunk_frames < 1:
             raise ValueError("chunk_frames >= 1")
         n = len(conds)
@@ -393,7 +413,8 @@ class Zonos:
             dec.reset(s)  # (an earlier stream_batch closed before its end)
         queue = sorted(range(n), key=lambda i: -mnt[i])  # longest-processing-time first, so the tail is short
         owner = [-1] * slots
-        rounds = BatchRounds(e, ae, dec, slots, chunk_frames)  # the round serve() runs too (serving.py)
+        rs = None if rate is None else self._stream_resampler(rate, slots)
+        rounds = BatchRounds(e, ae, dec, slots, chunk_frames, rs)  # the round serve() runs too (serving.py)
 
         def fill():
             items = []
@@ -404,6 +425,8 @@ class Zonos:
                     items.append((s, conds[i], prefixes[i], mnt[i], params))
                     owner[s] = i
                     rounds.start(s, plen[i], mnt[i])
+                    if rs is not None:
+                        rs.reset(s)
             e.prefill_many(items)
 
         try:
@@ -418,18 +441,41 @@ class Zonos:
         finally:
             for s in range(slots):
                 dec.reset(s)
+                if rs is not None:
+                    rs.reset(s)
                 if owner[s] >= 0:
                     e.release(s)
 
     def serve(self, max_slots: int, max_seqlen: int, max_prefill: int, chunk_frames: int = 16,
-              pcm16: bool = False) -> ServeSession:
+              pcm16: bool = False, sample_rate: int | None = None) -> ServeSession:
         """A serving session (serving.ServeSession, a context manager): submit() requests from any thread while
         others are being spoken, run_round() from one thread hands out every ticket's chunks, each ticket's
         concatenated bit for bit decode(generate_batch()) of the request alone; with pcm16 they leave as int16 CPU
-        tensors (zmi_pcm16_pack). Capacity is fixed here; while the session is open generate(), stream(),
-        generate_batch(), stream_batch() and another serve() raise RuntimeError."""
+        tensors (zmi_pcm16_pack); with sample_rate they leave at that rate (zmi_resample between the round's waveforms
+        and the egress; None or 44100: no resampler, the unchanged path). Capacity is fixed here; while the session is
+        open generate(), stream(), generate_batch(), stream_batch() and another serve() raise RuntimeError."""
         self._check_not_serving("serve")
-        return ServeSession(self, max_slots, max_seqlen, max_prefill, chunk_frames, pcm16)
+        return ServeSession(self, max_slots, max_seqlen, max_prefill, chunk_frames, pcm16, sample_rate)
+
+    def _output_rate(self, sample_rate):
+        """None for the decoder's own 44.1 kHz (no resampler), else the validated rate."""
+        if sample_rate is None:
+            return None
+        from .config import DAC_SAMPLE_RATE
+        from .resampling import resample_plan
+        resample_plan(DAC_SAMPLE_RATE, sample_rate)  # ValueError for a bad rate, before anything is built
+        return None if sample_rate == DAC_SAMPLE_RATE else int(sample_rate)
+
+    def _stream_resampler(self, rate: int, lanes: int):
+        """The streaming resampler of stream() / stream_batch() / serve() to `rate`, every lane reset; kept (its table
+        and carry buffers stay on the device)."""
+        key = (id(self.autoencoder), rate)
+        rs = self._stream_resamplers.get(key)
+        if rs is None or rs.lanes < lanes:
+            rs = self._stream_resamplers[key] = self.autoencoder.resampler(rate, lanes)
+        for lane in range(rs.lanes):
+            rs.reset(lane)
+        return rs
 
     def _check_not_serving(self, what: str):
         if self._serving is not None:

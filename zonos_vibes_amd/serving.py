@@ -171,9 +171,10 @@ class BatchRounds:
     next round's steps wait for the autoencoder's stream. The state is read before the push, so nothing is decoded past
     an utterance's end."""
 
-    def __init__(self, engine, autoencoder, decoder, slots: int, chunk_frames: int):
+    def __init__(self, engine, autoencoder, decoder, slots: int, chunk_frames: int, resampler=None):
         import torch
         from .engine import ST_FIELDS
+        self.rs = resampler  # a StreamResampler over the slots (sample_rate), or None: the waveforms leave as decoded
         self.e, self.ae, self.dec, self.slots, self.chunk = engine, autoencoder, decoder, int(slots), int(chunk_frames)
         self.sizes = size_buckets(self.slots)
         self.plen, self.mnt = [0] * self.slots, [0] * self.slots
@@ -189,8 +190,9 @@ class BatchRounds:
 
     def round(self, busy, egress=None) -> tuple:
         """One round over the busy slots -> ({slot: fp32 waveform [1, 1, 512 n] of the round, for the slots with
-        audio or that ended}, the slots that ended). egress(wavs), if given, is called on the engine's stream
-        behind the round's windows (the PCM16 pack)."""
+        audio or that ended}, the slots that ended). With a resampler the waveforms go through ONE push of it first
+        (the ended slots as final) and leave at its rate, [1, 1, any n >= 0]. egress(wavs), if given, is called on the
+        engine's stream behind the round's windows (the PCM16 pack)."""
         import torch
         from .engine import codes_count
         e, dec, fields = self.e, self.dec, self.fields
@@ -228,6 +230,8 @@ class BatchRounds:
                 wavs[s] = tail if w is None or w.shape[-1] == 0 else \
                     w if tail.shape[-1] == 0 else torch.cat([w, tail], dim=-1)
             wavs = {s: wavs[s] for s in sorted(wavs) if wavs[s].shape[-1] or s in tails}
+            if self.rs is not None and wavs:
+                wavs = self.rs.push(wavs, final=ended)
             if egress is not None:
                 egress(wavs)
         self.cur.wait_stream(e.stream)
@@ -313,14 +317,16 @@ class Pcm16Egress:
 class ServeSession:
     """Zonos.serve(): see the module docstring. For every ticket the chunks concatenated are, bit for bit,
     autoencoder.decode(generate_batch([cond], [prefix], max_new_tokens=[n], cfg_scale=c, sampling_params=sp,
-    seeds=[seed])[0]) (with pcm16, that waveform's clamp(-1, 1) * 32767 truncated to int16), whenever the request was
+    seeds=[seed])[0]) (with sample_rate, autoencoder.resample(that, 44100, sample_rate); with pcm16, the waveform's
+    clamp(-1, 1) * 32767 truncated to int16, a launch of its own behind the resampler's), whenever the request was
     admitted, whichever slot it got and whatever the other slots were doing: the stepping kernels are row-invariant.
     Every ticket that is not cancelled gets exactly one item with last = True (its chunk may be empty)."""
 
     def __init__(self, model, max_slots: int, max_seqlen: int, max_prefill: int, chunk_frames: int = 16,
-                 pcm16: bool = False):
+                 pcm16: bool = False, sample_rate: int | None = None):
         if chunk_frames < 1:
             raise ValueError("chunk_frames >= 1")
+        rate = model._output_rate(sample_rate)  # None: 44.1 kHz, the path without a resampler
         if getattr(model, "_serving", None) is not None:
             raise RuntimeError("a serve() session is already open on this model")
         self.model, self.pcm16 = model, bool(pcm16)
@@ -334,7 +340,8 @@ class ServeSession:
         for s in range(max_slots):
             dec.reset(s)
         self.dec = dec
-        self.rounds = BatchRounds(e, ae, dec, max_slots, chunk_frames)
+        self.rs = None if rate is None else model._stream_resampler(rate, max_slots)  # kept, every lane reset
+        self.rounds = BatchRounds(e, ae, dec, max_slots, chunk_frames, self.rs)
         self.egress = Pcm16Egress(e.dev, max_slots, chunk_frames) if self.pcm16 else None
         self.rounds_run = 0
         self._open = True
@@ -369,7 +376,8 @@ class ServeSession:
     def run_round(self) -> list:
         """One round: cancellations, admissions (one prefill_many), the steps, and the round's audio as
         [(ticket, chunk, last)]: fp32 device tensors [1, 1, 512 n] as stream_batch() yields them, or with pcm16
-        int16 CPU tensors. [] at once when nothing is running or waiting."""
+        int16 CPU tensors; with sample_rate a chunk has any length >= 0. [] at once when nothing is running or
+        waiting."""
         import torch
         if not self._open:
             raise RuntimeError("the session is closed")
@@ -378,11 +386,15 @@ class ServeSession:
             released, admitted = self.sched.begin_round()
             for s in released:
                 self.dec.reset(s)
+                if self.rs is not None:
+                    self.rs.reset(s)
                 e.release(s)
             if admitted:
                 e.prefill_many([(s, *r.payload[:2], r.max_new_tokens, r.payload[2]) for s, r in admitted])
                 for s, r in admitted:
                     rounds.start(s, r.p, r.max_new_tokens)
+                    if self.rs is not None:
+                        self.rs.reset(s)
             busy = self.sched.busy()
             if not busy:
                 return []
@@ -409,6 +421,8 @@ class ServeSession:
             busy = self.sched.release_all()
             for s in range(self.sched.max_slots):
                 self.dec.reset(s)
+                if self.rs is not None:
+                    self.rs.reset(s)
             for s in busy:
                 self.model.engine.release(s)
         finally:
