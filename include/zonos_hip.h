@@ -357,10 +357,10 @@ int zmi_resample_carry(const ZmiResampleSeg* segs, const ZmiResampleSeg* segs_ho
 
 /* ---------------------------------------------------------------------------------------
  * Speaker encoder (Zonos.make_speaker_embedding, model.py:90-95 -> SpeakerEmbeddingLDA, speaker_cloning.py:388-412:
- * ResNet293 with SimAM blocks). Activations are fp16 channels-last [H][W][C] (H the mel axis, W time, batch 1);
- * conv weights fp16 channel-blocked per tap [tap = ky k + kx][Ci/32][Co][32]; fp32 accumulation on MFMA. Every
- * reduction runs in a fixed order (no floating-point atomics): two runs give the same bits. The LDS opt-in of the
- * conv kernel failing is an error.
+ * ResNet293 with SimAM blocks). Activations are fp16 channels-last [H][W][C] (H the mel axis, W time; the _lanes
+ * entry points take many clips of their own W); conv weights fp16 channel-blocked per tap
+ * [tap = ky k + kx][Ci/32][Co][32]; fp32 accumulation on MFMA. Every reduction runs in a fixed order (no
+ * floating-point atomics): two runs give the same bits. The LDS opt-in of the conv kernel failing is an error.
  * ------------------------------------------------------------------------------------- */
 /* Conv2d(Ci, Co, k, stride, padding = k / 2, bias = False) + eval-mode BatchNorm2d (+ ReLU) (speaker_cloning.py:69-72,
  * 79-80, 84-85): y[ho][wo][co] = act(acc * scale[co] + shift[co]) in fp32, stored fp16; k in {1, 3}, stride in {1, 2},
@@ -380,6 +380,31 @@ int zmi_spk_stem(const void* x, int H, int W, const void* w, const float* scale,
 int zmi_spk_simam(const void* x, const void* residual, int H, int W, int C, const float* psum, int n_psum, float* ws,
                   void* y, void* stream);
 int64_t zmi_spk_simam_ws_floats(int H, int W, int C);
+/* The three trunk entry points over `n` clips of one H and their own widths in one launch (ragged lanes,
+ * SpeakerEmbeddingLDA.embed_features_batch). The HOST struct is copied into the kernel arguments: no device table.
+ * Lane l's buffer is base + l * ls (ls_* in elements of the buffer's type), laid out [H][w[l]][C] exactly as the single
+ * form lays it out; w, scale and shift are shared. The grid's z is the lane and its x is sized for the widest lane; a
+ * workgroup past its own lane's tiles / chunks / positions returns at once. A lane's tile index (psum row), padding
+ * tests, SimAM chunks and row counts are those of its own width, so every element has the bits the single entry point
+ * gives that lane alone, and nothing outside a lane's own extent is written. The single entry points are these with
+ * n = 1 (strides ignored). Error (no launch): n < 1 or > ZMI_SPK_MAX_LANES, a w[l] < 1 (SimAM: H w[l] < 2), whatever
+ * the single form rejects (its size limit applies to the widest lane), and, when n > 1, a present buffer's stride
+ * below the widest lane's extent (H wmax C for activations, zmi_spk_conv2d_tiles(H, wmax, k, stride) Co for psum,
+ * max n_psum[l] C for SimAM's psum, zmi_spk_simam_ws_floats(H, wmax, C) for ws) or an fp16 activation stride that is
+ * no multiple of 8 (the 16-byte accesses). */
+#define ZMI_SPK_MAX_LANES 32
+typedef struct ZmiSpkLanes { int n; int w[ZMI_SPK_MAX_LANES]; } ZmiSpkLanes;
+int zmi_spk_max_lanes(void);  /* ZMI_SPK_MAX_LANES of this build */
+int zmi_spk_conv2d_lanes(const void* x, int H, const ZmiSpkLanes* lanes, int Ci, const void* w, const float* scale,
+                         const float* shift, int Co, int k, int stride, int relu, void* y, float* psum, int64_t ls_x,
+                         int64_t ls_y, int64_t ls_psum, void* stream);
+int zmi_spk_stem_lanes(const void* x, int H, const ZmiSpkLanes* lanes, const void* w, const float* scale,
+                       const float* shift, int Co, void* y, int64_t ls_x, int64_t ls_y, void* stream);
+/* n_psum: HOST array of n row counts (lane l's psum holds n_psum[l] rows: its own conv's tiles), with psum or NULL.
+ * Within a lane's ws the layout is the single form's at the widest lane's chunk count. y may be x (then ls_y = ls_x). */
+int zmi_spk_simam_lanes(const void* x, const void* residual, int H, const ZmiSpkLanes* lanes, int C, const float* psum,
+                        const int* n_psum, float* ws, void* y, int64_t ls_x, int64_t ls_res, int64_t ls_psum,
+                        int64_t ls_ws, int64_t ls_y, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Prefix conditioner (Zonos.prepare_conditioning, model.py:204-212 -> PrefixConditioner.forward,

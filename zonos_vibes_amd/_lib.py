@@ -81,6 +81,20 @@ class CondRow(ctypes.Structure):
     _fields_ = [("param", c_int), ("kind", c_int), ("index", c_int), ("x_off", c_int)]
 
 
+SPK_MAX_LANES = 32  # ZMI_SPK_MAX_LANES
+
+
+class SpkLanes(ctypes.Structure):
+    """ZmiSpkLanes: the clips of one ragged launch of the speaker trunk, each with its own width (frames)."""
+    _fields_ = [("n", c_int), ("w", c_int * SPK_MAX_LANES)]
+
+    @classmethod
+    def of(cls, widths) -> "SpkLanes":
+        if not 1 <= len(widths) <= SPK_MAX_LANES:
+            raise ValueError(f"1 .. {SPK_MAX_LANES} lanes, got {len(widths)}")
+        return cls(len(widths), (c_int * SPK_MAX_LANES)(*widths))
+
+
 class Mamba2Args(ctypes.Structure):
     _fields_ = [
         ("zxbcdt", c_void_p), ("ld_zx", c_int), ("M", c_int),
@@ -164,6 +178,15 @@ _SIGS = {
     "zmi_spk_stem": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "zmi_spk_simam": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "zmi_spk_simam_ws_floats": (c_int64, [c_int, c_int, c_int]),
+    "zmi_spk_max_lanes": (c_int, []),
+    "zmi_spk_conv2d_lanes": (c_int, [c_void_p, c_int, ctypes.POINTER(SpkLanes), c_int, c_void_p, c_void_p, c_void_p,
+                                     c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_int64, c_int64,
+                                     c_void_p]),
+    "zmi_spk_stem_lanes": (c_int, [c_void_p, c_int, ctypes.POINTER(SpkLanes), c_void_p, c_void_p, c_void_p, c_int,
+                                   c_void_p, c_int64, c_int64, c_void_p]),
+    "zmi_spk_simam_lanes": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(SpkLanes), c_int, c_void_p,
+                                    ctypes.POINTER(c_int), c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64,
+                                    c_int64, c_void_p]),
     "zmi_prefix_condition": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_float,
                                      c_void_p, c_void_p]),
     "zmi_mamba2_step": (c_int, [ctypes.POINTER(Mamba2Args), c_void_p]),

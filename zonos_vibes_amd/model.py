@@ -119,16 +119,30 @@ class Zonos:
         from .speaker import SpeakerEmbeddingLDA
         self.spk_clone_model = SpeakerEmbeddingLDA.from_files(ckpt_path, lda_path, self._device)
 
-    def make_speaker_embedding(self, wav: torch.Tensor, sr: int) -> torch.Tensor:
-        """model.py:90-95: [channels, N] (or [N]) waveform at `sr` -> [1, 1, 128] bf16 for make_cond_dict(speaker=)."""
+    def _speaker_model(self):
+        """The loaded speaker encoder, or (Zonos.synthetic) the synthetic one, created on first use."""
         if self.spk_clone_model is None:
             if self._spk_synthetic_seed is None:
                 raise RuntimeError("no speaker encoder weights: call load_speaker_model(ckpt_path, lda_path) first "
                                    "(this build does not download them)")
             from .speaker import SpeakerEmbeddingLDA
             self.spk_clone_model = SpeakerEmbeddingLDA(self._device, seed=self._spk_synthetic_seed)
-        _, spk_embedding = self.spk_clone_model(wav.to(self._device), sr)
+        return self.spk_clone_model
+
+    def make_speaker_embedding(self, wav: torch.Tensor, sr: int) -> torch.Tensor:
+        """model.py:90-95: [channels, N] (or [N]) waveform at `sr` -> [1, 1, 128] bf16 for make_cond_dict(speaker=)."""
+        _, spk_embedding = self._speaker_model()(wav.to(self._device), sr)
         return spk_embedding.unsqueeze(0).bfloat16()
+
+    def make_speaker_embeddings(self, wavs, srs) -> list:
+        """make_speaker_embedding for many clips (srs: one rate per clip, or one int for all): the ResNet trunk runs
+        over the clips as ragged lanes of one launch sequence per group (speaker.plan_lanes). Element i is bit-equal
+        to make_speaker_embedding(wavs[i], srs[i])."""
+        srs = [srs] * len(wavs) if isinstance(srs, int) else list(srs)
+        if len(srs) != len(wavs):
+            raise ValueError(f"{len(wavs)} clips but {len(srs)} sample rates")
+        _, lda = self._speaker_model().embed_batch([(w.to(self._device), sr) for w, sr in zip(wavs, srs)])
+        return [lda[i:i + 1].unsqueeze(0).bfloat16() for i in range(len(wavs))]
 
     # ------------------------------------------------------------------ conditioning
     def prepare_conditioning(self, cond_dict: dict, uncond_dict: dict | None = None) -> torch.Tensor:

@@ -2,11 +2,14 @@
 
     enc = SpeakerEmbeddingLDA("cuda")                       # synthetic weights, or state_dict= / from_files(...)
     emb, lda = enc(wav, sample_rate)                        # [1, 256] fp32, [1, 128] fp32
+    embs, ldas = enc.embed_batch([(wav, sample_rate), ..])  # [B, 256], [B, 128]: row i has the bits of enc(clip i)
 
 The ResNet293 trunk (stem, 97 SimAM blocks: 3x3 / 1x1 convs with eval BatchNorm, SimAM, residual) runs on the
 kernels of csrc/zmi_spk.hip: fp16 channels-last activations, fp16 channel-blocked weights, fp32 accumulation and
 fp32 BatchNorm scale / shift. The front end (mono mean, resampling to 16 kHz, log-mel filterbank) and the tail
-(attentive statistics pooling, bottleneck, LDA; < 0.1 % of the work) are fp32 torch ops on the device.
+(attentive statistics pooling, bottleneck, LDA; < 0.1 % of the work) are fp32 torch ops on the device. A batch of clips
+runs the trunk as ragged lanes (one launch sequence for a group of clips, each with its own frame count: `plan_lanes`,
+`front_lanes`); the front end and the tail stay per clip, so every clip keeps the bits of its single call.
 
 torchaudio is absent in this build: the resampler and the filterbank restate its documented defaults
 (`Resample`: Hann-windowed sinc, lowpass_filter_width 6, rolloff 0.99; `MelSpectrogram`: n_fft 512, periodic Hann
@@ -148,6 +151,25 @@ def log_fbank(wav: torch.Tensor, basis: torch.Tensor, fb: torch.Tensor) -> torch
     return out - out.mean(dim=1, keepdim=True)
 
 
+# ------------------------------------------------------------------------------------- lanes
+def plan_lanes(frames: list, max_lanes: int = _lib.SPK_MAX_LANES, max_lane_frames: int = 32768) -> list:
+    """Groups of clip indices, each one ragged launch sequence of the trunk: longest clips first (ties by index), at
+    most `max_lanes` clips per group and len(group) x the group's longest clip <= `max_lane_frames`; a clip longer
+    than that is a group of its own. The workspace holds len(group) lanes of the longest clip, and its three
+    activation buffers take 3 x acoustic_dim x in_planes x 2 B = 30,720 B per lane-frame at full size, so the default
+    bounds them at 32768 x 30,720 B = 1.0 GB."""
+    if not 1 <= max_lanes <= _lib.SPK_MAX_LANES or max_lane_frames < 1:
+        raise ValueError(f"max_lanes must be 1 .. {_lib.SPK_MAX_LANES} and max_lane_frames >= 1")
+    groups = []
+    for i in sorted(range(len(frames)), key=lambda i: (-frames[i], i)):
+        g = groups[-1] if groups else None  # the group's first clip is its longest
+        if g is None or len(g) == max_lanes or (len(g) + 1) * frames[g[0]] > max_lane_frames:
+            groups.append([i])
+        else:
+            g.append(i)
+    return groups
+
+
 # ------------------------------------------------------------------------------------- the encoder
 class SpeakerEmbeddingLDA:
     def __init__(self, device="cuda", state_dict: dict | None = None, lda_state_dict: dict | None = None, seed: int = 0,
@@ -175,7 +197,8 @@ class SpeakerEmbeddingLDA:
         self._prepare(state_dict, lda_state_dict)
         self._basis = dft_basis().to(self.dev)
         self._fb = mel_filterbank(n_mels=config.acoustic_dim).to(self.dev)
-        self._w_cap = 0
+        self._lane_sizes = {}                                  # widest W -> one lane's elements per workspace buffer
+        self._cap = dict(act=0, x16=0, psum=0, ws=0)           # elements allocated
 
     @classmethod
     def from_files(cls, ckpt_path: str, lda_path: str, device="cuda",
@@ -213,22 +236,27 @@ class SpeakerEmbeddingLDA:
         self.bott_w, self.bott_b = f32(sd["bottleneck.weight"]), f32(sd["bottleneck.bias"])
         self.lda_w, self.lda_b = f32(lda["weight"]), f32(lda["bias"])
 
-    def _workspace(self, W: int):
+    def _workspace(self, W: int, lanes: int = 1):
         """Three fp16 activation buffers (two ping-pong plus the residual) and the SimAM sums, sized from the frame
-        count and grown on demand. The largest activation is the stem's [acoustic_dim][W][in_planes]."""
-        if W > self._w_cap:
-            cfg = self.config
-            n = cfg.acoustic_dim * W * cfg.in_planes
-            self._acts = [torch.empty(n, dtype=torch.float16, device=self.dev) for _ in range(3)]
-            self._x16 = torch.empty(cfg.acoustic_dim * W, dtype=torch.float16, device=self.dev)
+        count and grown on demand. The largest activation is the stem's [acoustic_dim][W][in_planes]. With lanes,
+        W is the widest lane and every buffer holds `lanes` of them, lane l at l * `self._ls[buffer]` elements (the
+        same stride at every stage: later stages are smaller)."""
+        cfg = self.config
+        if W not in self._lane_sizes:
             psum = ws = 0  # the largest stage's per-tile sums and SimAM workspace
             for li in range(4):
                 h, w, c = (cfg.acoustic_dim - 1) // (1 << li) + 1, (W - 1) // (1 << li) + 1, cfg.in_planes << li
                 psum = max(psum, self.lib.zmi_spk_conv2d_tiles(h, w, 3, 1) * c)
                 ws = max(ws, self.lib.zmi_spk_simam_ws_floats(h, w, c))
-            self._psum = torch.empty(psum, dtype=torch.float32, device=self.dev)
-            self._ws = torch.empty(ws, dtype=torch.float32, device=self.dev)
-            self._w_cap = W
+            self._lane_sizes[W] = dict(act=cfg.acoustic_dim * W * cfg.in_planes, x16=cfg.acoustic_dim * W, psum=psum,
+                                       ws=ws)
+        self._ls = self._lane_sizes[W]
+        if any(lanes * n > self._cap[k] for k, n in self._ls.items()):
+            self._cap = {k: max(lanes * n, self._cap[k]) for k, n in self._ls.items()}
+            self._acts = [torch.empty(self._cap["act"], dtype=torch.float16, device=self.dev) for _ in range(3)]
+            self._x16 = torch.empty(self._cap["x16"], dtype=torch.float16, device=self.dev)
+            self._psum = torch.empty(self._cap["psum"], dtype=torch.float32, device=self.dev)
+            self._ws = torch.empty(self._cap["ws"], dtype=torch.float32, device=self.dev)
         return self._acts
 
     # --------------------------------------------------------------- trunk
@@ -276,6 +304,53 @@ class SpeakerEmbeddingLDA:
             rec(blk["name"], b0, H, W, c)
         return b0[: H * W * c].view(H, W, c)
 
+    @torch.inference_mode()
+    def front_lanes(self, feats: list) -> list:
+        """`front` for up to 32 clips as ragged lanes of one launch sequence: feats [acoustic_dim, W_l] fp32 each ->
+        views [H / 8, W_l / 8, 8 in_planes] fp16 of the workspace, each with the bits `front` gives that clip alone.
+        The launches are those of one clip; every lane keeps its own width down the stages."""
+        cfg, p, lib = self.config, _lib.ptr, self.lib
+        H = cfg.acoustic_dim
+        if any(f.ndim != 2 or f.shape[0] != H or f.shape[1] < 2 for f in feats):
+            raise ValueError(f"features must be [{H}, frames >= 2], got {[tuple(f.shape) for f in feats]}")
+        ws = [int(f.shape[1]) for f in feats]
+        sptr = torch.cuda.current_stream(self.dev).cuda_stream
+        b0, b1, b2 = self._workspace(max(ws), len(ws))
+        ls = self._ls
+        for l, f in enumerate(feats):
+            self._x16[l * ls["x16"]: l * ls["x16"] + H * ws[l]].copy_(f.reshape(-1))
+        c, L = cfg.in_planes, _lib.SpkLanes.of(ws)
+        _lib.check(lib.zmi_spk_stem_lanes(p(self._x16), H, L, p(self.stem_w), p(self.stem_bn[0]), p(self.stem_bn[1]), c,
+                                          p(b0), ls["x16"], ls["act"], sptr), "spk_stem_lanes")
+
+        def conv(x, h, lanes, cv, bnp, stride, relu, y, psum=None):
+            _lib.check(lib.zmi_spk_conv2d_lanes(p(x), h, lanes, cv["ci"], p(cv["w"]), p(bnp[0]), p(bnp[1]), cv["co"],
+                                                cv["k"], stride, int(relu), p(y), p(psum), ls["act"], ls["act"],
+                                                ls["psum"], sptr), "spk_conv2d_lanes")
+
+        tiles = None
+        for blk in self.blocks:
+            s, co = blk["stride"], blk["c1"]["co"]
+            Lo, ho = L, H
+            if s != 1 or tiles is None:  # the widths change: this stage's lanes and their conv2 tile counts
+                ho, ws = (H - 1) // s + 1, [(w - 1) // s + 1 for w in ws]
+                Lo = _lib.SpkLanes.of(ws)
+                tiles = (_lib.c_int * len(ws))(*[lib.zmi_spk_conv2d_tiles(ho, w, 3, 1) for w in ws])
+            conv(b0, H, L, blk["c1"], blk["bn1"], s, True, b1)
+            if blk["ds"] is None:
+                conv(b1, ho, Lo, blk["c2"], blk["bn2"], 1, False, b2, self._psum)
+                x, res, out = b2, b0, b1
+            else:
+                conv(b0, H, L, blk["ds"], blk["dsbn"], s, False, b2)
+                conv(b1, ho, Lo, blk["c2"], blk["bn2"], 1, False, b0, self._psum)
+                x, res, out = b0, b2, b1
+            _lib.check(lib.zmi_spk_simam_lanes(p(x), p(res), ho, Lo, co, p(self._psum), tiles, p(self._ws), p(out),
+                                               ls["act"], ls["act"], ls["psum"], ls["ws"], ls["act"], sptr),
+                       "spk_simam_lanes")
+            b0, b1, b2 = out, x, res
+            H, L, c = ho, Lo, co
+        return [b0[l * ls["act"]: l * ls["act"] + H * w * c].view(H, w, c) for l, w in enumerate(ws)]
+
     # --------------------------------------------------------------- tail (fp32 torch ops on the device)
     def pool(self, front: torch.Tensor) -> torch.Tensor:
         """ASP (speaker_cloning.py:38-61) on the trunk's [H, W, C] output -> [1, 2 C H] fp32."""
@@ -301,6 +376,25 @@ class SpeakerEmbeddingLDA:
             record["front"] = fr.permute(2, 0, 1)[None].float()
             record["pooled"] = pooled
         return emb, lda
+
+    @torch.inference_mode()
+    def embed_features_batch(self, feats: list, max_lanes: int = _lib.SPK_MAX_LANES, max_lane_frames: int = 32768):
+        """`embed_features` for many clips: feats [acoustic_dim, W_i] each -> (emb [B, embd], lda [B, lda]) fp32 in the
+        caller's order, row i with the bits embed_features(feats[i]) gives. The trunk runs once per group of
+        `plan_lanes` (one clip's launches for the whole group); the tail stays per clip, on the clip's own slice, so
+        rocBLAS sees the single form's shapes."""
+        feats = [f.to(self.dev, torch.float32) for f in feats]
+        emb = torch.empty(len(feats), self.config.embd_dim, dtype=torch.float32, device=self.dev)
+        lda = torch.empty(len(feats), self.config.lda_dim, dtype=torch.float32, device=self.dev)
+        for group in plan_lanes([int(f.shape[-1]) for f in feats], max_lanes, max_lane_frames):
+            for i, fr in zip(group, self.front_lanes([feats[i] for i in group])):
+                e = self.pool(fr) @ self.bott_w.t() + self.bott_b
+                emb[i], lda[i] = e[0], (e @ self.lda_w.t() + self.lda_b)[0]
+        return emb, lda
+
+    def embed_batch(self, clips: list, max_lanes: int = _lib.SPK_MAX_LANES, max_lane_frames: int = 32768):
+        """`__call__` for many clips [(wav, sample_rate), ..]: the front end per clip, then embed_features_batch."""
+        return self.embed_features_batch([self.features(w, sr) for w, sr in clips], max_lanes, max_lane_frames)
 
     @torch.inference_mode()
     def features(self, wav: torch.Tensor, sample_rate: int) -> torch.Tensor:
