@@ -310,6 +310,33 @@ int zmi_dac_conv_t_lanes(const void* x, int t_in, int c_in, const void* w_phases
                          int64_t ls_x, int64_t ls_raw, int64_t ls_snake, void* stream);
 int zmi_dac_conv_out_range_lanes(const void* x, int t, int c_in, const void* w_pad, const float* bias_pad, int q0,
                                  int n, float* out, int lanes, int64_t ls_x, int64_t ls_out, void* stream);
+/* Range form of zmi_dac_conv_t_lanes (the carried-state streaming decoder's transposed conv): output rows n0 .. n0 + n
+ * - 1 only, written to out rows 0 .. n - 1 (out_raw / out_snake point at row n0; lane strides as above, extent n c_out).
+ * x row 0 is input row x0 of the utterance and t_in rows are given; rows outside them are zeros. The range need not
+ * be aligned to the stride (a streaming frontier is stride F - pad): every phase has its own q range. Each row has the
+ * bits zmi_dac_conv_t_lanes gives it and nothing outside the range is written; n = 0 launches nothing. Error (no
+ * launch) unless stride >= 2, 0 <= n0, 0 <= n, n0 + n <= stride (x0 + t_in) and the first row read, (n0 + pad) / stride - 1, is
+ * >= x0 or is the zero padding before row 0 (x0 = 0). */
+int zmi_dac_conv_t_range_lanes(const void* x, int x0, int t_in, int c_in, const void* w_phases, const float* bias,
+                               int c_out, int stride, int pad, int n0, int n, void* out_raw, void* out_snake,
+                               const float* alpha, int lanes, int64_t ls_x, int64_t ls_raw, int64_t ls_snake,
+                               void* stream);
+/* Carried-state streaming decode: copies between a per-lane state pool (pool_lanes lanes of pool_lane_units each) and
+ * the dense scratch of one launch sequence, ONE launch over all lanes and segments. Units are 16 bytes (one vector
+ * load / store). For group lane l = 0 .. lanes - 1, pool lane lane_ids[l] (DEVICE int32 array; any subset of the
+ * pool, in any order, no id twice in a scatter) and every segment: pool[id][pool_off .. + count) <->
+ * scratch[scratch_off + l scratch_ls .. + count); mode ZMI_DAC_MOVE_GATHER copies pool -> scratch, _SCATTER scratch ->
+ * pool, _ZERO writes zeros to the scratch segments (the zero state of an utterance's first push; the pool is not
+ * read). segs is a HOST array of n_segs <= ZMI_DAC_MOVE_SEGS segments. Nothing outside the segments is written; an id
+ * outside the pool moves nothing. Error (no launch) on another mode, when a segment leaves a lane's state or the
+ * scratch, or scratch_ls < count with lanes > 1. */
+#define ZMI_DAC_MOVE_SEGS 48
+#define ZMI_DAC_MOVE_GATHER 0
+#define ZMI_DAC_MOVE_SCATTER 1
+#define ZMI_DAC_MOVE_ZERO 2
+typedef struct ZmiDacMoveSeg { uint32_t pool_off, scratch_off, count, scratch_ls; } ZmiDacMoveSeg;
+int zmi_dac_state_move(void* pool, int64_t pool_lane_units, int pool_lanes, void* scratch, int64_t scratch_units,
+                       const int* lane_ids, int lanes, const ZmiDacMoveSeg* segs, int n_segs, int mode, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * PCM16 egress (the reference server's float -> 16-bit PCM conversion, server.py:142-146:

@@ -156,7 +156,7 @@ def end_to_end(args, dev) -> dict:
     off_s, tot_s = statistics.median(off), statistics.median(tot)
     first = firsts[len(firsts) // 2]
     pct = lambda q: round(first[min(int(q * len(first)), len(first) - 1)], 1)  # noqa: E731
-    dec = model._stream_batch_decoders[(id(model.autoencoder), CHUNK)].decode_windows
+    dec = model._stream_batch_decoders[(id(model.autoencoder), CHUNK, False)].decode_windows
     chunk_ms = CHUNK * DAC_HOP / DAC_SAMPLE_RATE * 1e3
     return dict(workload=f"C3 share: utterances 0..{n - 1} of the 512-utterance C3 set (2-30 s, Lc 8 + 15 s), {slots} "
                          f"slots on one GPU, greedy, EOS suppressed, chunk_frames {CHUNK}",

@@ -162,6 +162,11 @@ _SIGS = {
                                      c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p]),
     "zmi_dac_conv_out_range_lanes": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
                                              c_int64, c_int64, c_void_p]),
+    "zmi_dac_conv_t_range_lanes": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                           c_int, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64,
+                                           c_void_p]),
+    "zmi_dac_state_move": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int, c_int,
+                                   c_void_p]),
     "zmi_pcm16_pack": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p]),
     "zmi_resample": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "zmi_resample_carry": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
@@ -215,7 +220,7 @@ _SIGS = {
 
 EXPORTED = sorted(_SIGS)
 _lib = None
-ABI_VERSION = 8  # zmi_version() of the library this binding (and its weight packers) is written for
+ABI_VERSION = 9  # zmi_version() of the library this binding (and its weight packers) is written for
 
 
 def load(path: str = LIB_PATH) -> ctypes.CDLL:

@@ -20,8 +20,8 @@ from . import _lib
 from . import synthetic as syn
 from .config import DAC_HOP, DAC_SAMPLE_RATE, N_CODEBOOKS
 from .resampling import GpuResampler, StreamResampler, resample_plan
-from .streaming import (DAC_LOOKAHEAD_FRAMES, DACBatchStreamDecoder, DACStreamDecoder,  # noqa: F401
-                        dac_lookahead_frames)
+from .streaming import (DAC_LOOKAHEAD_FRAMES, CarryLayout, DACBatchStreamDecoder, DACCarryBatchStreamDecoder,  # noqa: F401
+                        DACCarryStreamDecoder, DACStreamDecoder, dac_lookahead_frames)
 
 STRIDES = syn.DAC_STRIDES
 ENC_STRIDES = syn.DAC_ENC_STRIDES
@@ -126,6 +126,7 @@ class _WindowDecoder:
         self._bufs = None
         self._graph = None
         self.graph_replays = 0
+        self.frames_computed = 0  # code frames decoded (a window's halo frames count)
 
     def _alloc(self):
         ae = self.ae
@@ -137,6 +138,7 @@ class _WindowDecoder:
         ae = self.ae
         W = codes.shape[1]
         assert 0 <= f0 < f1 <= W <= self.wmax, (f0, f1, W)
+        self.frames_computed += W
         cur = torch.cuda.current_stream(ae.dev)
         ae.stream.wait_stream(cur)
         with torch.cuda.stream(ae.stream):
@@ -188,6 +190,7 @@ class _BatchWindowDecoder:
         self._bufs = None
         self.lane_launches = 0  # _decode_lanes launch sequences issued
         self.lanes_decoded = 0  # windows decoded in them
+        self.frames_computed = 0  # code frames decoded in them (the single windows count theirs)
 
     def _reserve(self, lanes: int):
         if lanes > self._cap:
@@ -204,6 +207,7 @@ class _BatchWindowDecoder:
         self.ae._decode_lanes(torch.stack(windows), out, self._bufs, (DAC_HOP * f0, DAC_HOP * (f1 - f0)))
         self.lane_launches += 1
         self.lanes_decoded += n
+        self.frames_computed += n * W
         return [out[i].view(1, 1, -1) for i in range(n)]
 
     def __call__(self, windows: list) -> list:
@@ -229,6 +233,251 @@ class _BatchWindowDecoder:
                     o.record_stream(cur)
                     res[i] = o
         return res
+
+
+class _CarryState:
+    """The carried-state decoder's memory and launch sequence, shared by the single-utterance and the batched step:
+    a state pool [lanes][state halfs] fp16 (every CarryBuffer's `hist` rows, 425,856 bytes per lane for the DAC) and
+    a scratch arena with one dense [group lanes][hist | new][C] buffer per CarryBuffer, so no stage overwrites
+    another's input: _decode_one's in-place reuse (a unit's 1x1 conv writes over its own k7's input and over the
+    skip) would destroy rows the next push needs as history. A run is: gather (or zero, on an utterance's first
+    push) the history into the scratch, the decoder's 31 launches on [hist | new] through pointer offsets and in_off
+    (zmi_dac_conv_lanes as it is; zmi_dac_conv_t_range_lanes for the transposed convs, whose frontier s F - p is
+    not a multiple of the stride), scatter the tails back: 33 launches."""
+
+    def __init__(self, ae: "DACAutoencoder", lanes: int):
+        self.ae, self.lanes = ae, int(lanes)
+        self.layout = ae.carry_layout()
+        widths = {"z": ae.c1_cin, "c1": ae.c1_cout}
+        widths.update({j: blk["cout"] for j, blk in enumerate(ae.blocks)})
+        self.C = {b.name: widths[b.width] for b in self.layout.buffers.values()}
+        self.pool_off, off = {}, 0
+        for b in self.layout.buffers.values():
+            if b.hist:
+                self.pool_off[b.name] = off
+                off += b.hist * self.C[b.name]
+        self.state_halfs = off
+        assert off % 8 == 0 and len(self.pool_off) <= 48
+        with torch.cuda.stream(ae.stream):
+            self.pool = torch.zeros(self.lanes, off, dtype=torch.float16, device=ae.dev)
+        self._ids: dict = {}
+        self._layouts: dict = {}  # (plan key, lanes) -> scratch_halfs
+        self._segs: dict = {}     # (plan key, lanes, mode) -> the state-move table
+
+    def state_bytes_per_lane(self) -> int:
+        return 2 * self.state_halfs
+
+    def scratch_halfs(self, plan, B: int):
+        """{buffer: arena offset} and the arena's halfs for B lanes of this plan."""
+        got = self._layouts.get((plan.key, B))
+        if got is None:
+            got = self._layouts[(plan.key, B)] = self._scratch_halfs(plan, B)
+        return got
+
+    def _scratch_halfs(self, plan, B: int):
+        off, o, tmp = {}, 0, 0
+        for name, b in self.layout.buffers.items():
+            size = (B * plan.rows(name) * self.C[name] + 127) // 128 * 128
+            if b.hist:
+                off[name] = o
+                o += size
+            else:  # a k7's output, read by the 1x1 conv that follows and by nothing else: one region for all
+                tmp = max(tmp, size)
+        off.update({name: o for name, b in self.layout.buffers.items() if not b.hist})
+        return off, o + tmp
+
+    def lane_ids(self, ids) -> torch.Tensor:
+        key = tuple(ids)
+        if key not in self._ids:
+            if len(set(key)) != len(key) or not all(0 <= i < self.lanes for i in key):
+                raise ValueError(f"lanes {key}: distinct ids in [0, {self.lanes})")
+            if len(self._ids) >= 1024:  # (serve(): the subsets of slots that pushed equal n; kept small)
+                self._ids.clear()
+            self._ids[key] = torch.tensor(key, dtype=torch.int32, device=self.ae.dev)
+        return self._ids[key]
+
+    def _move(self, plan, ids_t, B, arena, off, mode):
+        arr = self._segs.get((plan.key, B, mode))
+        if arr is None:
+            segs = []
+            for name, po in self.pool_off.items():
+                c, hist = self.C[name], self.layout.buffers[name].hist
+                row = plan.tail[name] if mode == 1 else 0
+                segs += [po // 8, (off[name] + row * c) // 8, hist * c // 8, plan.rows(name) * c // 8]
+            arr = self._segs[(plan.key, B, mode)] = (ctypes.c_uint32 * len(segs))(*segs)
+        _lib.check(self.ae.lib.zmi_dac_state_move(self.pool.data_ptr(), self.state_halfs // 8, self.lanes,
+                                                  arena.data_ptr(), arena.numel() // 8, ids_t.data_ptr(), B, arr,
+                                                  len(arr) // 4, mode, self.ae.sptr), "dac_state_move")
+
+    def run(self, plan, ids_t: torch.Tensor, codes: torch.Tensor, arena: torch.Tensor, out: torch.Tensor):
+        """One CarryPlan over the lanes ids_t (int32, device): codes [B, 9, n] int64 contiguous -> out [B, hop m] fp32;
+        on the autoencoder's stream. The state is read unless the plan is an utterance's first and written unless
+        it is its last."""
+        ae, lay = self.ae, self.layout
+        B = codes.shape[0]
+        off, need = self.scratch_halfs(plan, B)
+        assert arena.numel() >= need and codes.is_contiguous() and out.is_contiguous()
+        lib, ck, C = ae.lib, _lib.check, self.C
+        base = arena.data_ptr()
+        P = lambda b, row=0: base + 2 * (off[b] + row * C[b])  # noqa: E731
+        LS = lambda b: plan.rows(b) * C[b]  # noqa: E731
+        hist = lambda b: lay.buffers[b].hist  # noqa: E731
+        self._move(plan, ids_t, B, arena, off, 2 if plan.first else 0)
+
+        def conv(st, w, bias, c_in, c_out, taps, alpha, skip=None, raw=None):
+            src, dst, n = st["src"], st["dst"], st["n_out"]
+            ck(lib.zmi_dac_conv_lanes(P(src), plan.rows(src), c_in, w.data_ptr(), bias.data_ptr(), c_out, taps,
+                                      st.get("d", 0), st["in_off"], n, 1, 0, n,
+                                      P(skip, st["skip_off"]) if skip else None, P(raw, hist(raw)) if raw else None,
+                                      P(dst, hist(dst)), alpha.data_ptr(), None, B, LS(src), LS(skip) if skip else 0,
+                                      LS(raw) if raw else 0, LS(dst), 0, ae.sptr), "dac_conv_lanes")
+
+        for st in plan.steps:
+            k, n = st["kind"], st["n_out"]
+            if n == 0:
+                continue
+            if k == "codes":
+                ck(lib.zmi_dac_from_codes_lanes(codes.data_ptr(), n, ae.codebooks.data_ptr(), ae.proj_w.data_ptr(),
+                                                ae.proj_b.data_ptr(), P("z", hist("z")), B, N_CODEBOOKS * n, LS("z"),
+                                                ae.sptr), "from_codes_lanes")
+            elif k == "k7" and "block" not in st:
+                conv(st, ae.c1_w, ae.c1_b, ae.c1_cin, ae.c1_cout, 7, ae.blocks[0]["alpha"])
+            elif k == "k7":
+                ru, c = ae.blocks[st["block"]]["res"][st["unit"]], ae.blocks[st["block"]]["cout"]
+                conv(st, ru["w1"], ru["b1"], c, c, 7, ru["a2"])
+            elif k == "pw":
+                j, u = st["block"], st["unit"]
+                blk = ae.blocks[j]
+                ru, c = blk["res"][u], blk["cout"]
+                if u + 1 < len(DILATIONS):
+                    nxt = blk["res"][u + 1]["a1"]
+                else:
+                    nxt = ae.blocks[j + 1]["alpha"] if j + 1 < len(ae.blocks) else ae.final_alpha
+                conv(st, ru["w2"], ru["b2"], c, c, 1, nxt, skip=st["skip"], raw=st["raw"])
+            elif k == "convt":
+                blk, src, dst, raw = ae.blocks[st["block"]], st["src"], st["dst"], st["raw"]
+                ck(lib.zmi_dac_conv_t_range_lanes(P(src), 0, plan.rows(src), blk["cin"], blk["wt"].data_ptr(),
+                                                  blk["bt"].data_ptr(), blk["cout"], blk["stride"], blk["pad"], st["n0"],
+                                                  n, P(raw, hist(raw)), P(dst, hist(dst)),
+                                                  blk["res"][0]["a1"].data_ptr(), B, LS(src), LS(raw), LS(dst), ae.sptr),
+                   "dac_conv_t_range_lanes")
+            else:
+                src = st["src"]
+                assert out.shape == (B, n), (out.shape, B, n)
+                ck(lib.zmi_dac_conv_out_range_lanes(P(src), plan.rows(src), C[src], ae.out_w.data_ptr(),
+                                                    ae.out_b.data_ptr(), st["in_off"] + 3, n, out.data_ptr(), B, LS(src),
+                                                    n, ae.sptr), "conv_out_range_lanes")
+        if not plan.final:
+            self._move(plan, ids_t, B, arena, off, 1)
+
+
+class _CarryStep:
+    """DACCarryStreamDecoder's decode_step on the HIP decoder: one lane of state; the steady-state step (a push of
+    chunk_frames frames past the utterance's start: one plan key whatever the position) is captured as a graph with
+    an arena, codes and output of its own."""
+
+    def __init__(self, ae: "DACAutoencoder", chunk_frames: int, capture: bool):
+        self.ae, self.chunk, self.capture = ae, int(chunk_frames), bool(capture)
+        self.state = _CarryState(ae, 1)
+        lay = self.state.layout
+        self.steady = lay.plan(lay.R + 1, self.chunk)
+        self._ids = self.state.lane_ids((0,))
+        self._arena = None
+        self._graph = None
+        self.graph_replays = 0
+        self.frames_computed = 0  # code frames decoded: a push's own
+
+    def reset(self):
+        pass  # an utterance's first push reads no state (ZMI_DAC_MOVE_ZERO)
+
+    def snapshot(self):
+        with torch.cuda.stream(self.ae.stream):  # ordered behind the pushes, which run on this stream
+            return self.state.pool.clone()
+
+    def restore(self, snap):
+        with torch.cuda.stream(self.ae.stream):
+            self.state.pool.copy_(snap)
+
+    def __call__(self, plan, codes: torch.Tensor) -> torch.Tensor:
+        ae, hop = self.ae, self.state.layout.hop
+        m = plan.emit1 - plan.emit0
+        self.frames_computed += plan.n
+        cur = torch.cuda.current_stream(ae.dev)
+        ae.stream.wait_stream(cur)
+        with torch.cuda.stream(ae.stream):
+            if self.capture and plan.key == self.steady.key:
+                if self._graph is None:
+                    self._garena = torch.empty(self.state.scratch_halfs(plan, 1)[1], dtype=torch.float16, device=ae.dev)
+                    self._gcodes = torch.zeros(1, N_CODEBOOKS, self.chunk, dtype=torch.int64, device=ae.dev)
+                    self._gout = torch.empty(1, hop * m, dtype=torch.float32, device=ae.dev)
+                    self._gcodes[0].copy_(codes)
+                    _lib.check(ae.lib.zmi_graph_begin(ae.sptr), "graph_begin")
+                    try:
+                        self.state.run(plan, self._ids, self._gcodes, self._garena, self._gout)
+                    finally:
+                        g = ctypes.c_void_p()
+                        _lib.check(ae.lib.zmi_graph_end(ae.sptr, ctypes.byref(g)), "graph_end")
+                    self._graph = g.value
+                else:
+                    self._gcodes[0].copy_(codes)
+                _lib.check(ae.lib.zmi_graph_launch(self._graph, 1, ae.sptr), "graph_launch")
+                self.graph_replays += 1
+                out = self._gout.clone()
+            else:
+                need = self.state.scratch_halfs(plan, 1)[1]
+                if self._arena is None or self._arena.numel() < need:
+                    self._arena = None
+                    self._arena = torch.empty(need, dtype=torch.float16, device=ae.dev)
+                out = torch.empty(1, hop * m, dtype=torch.float32, device=ae.dev)
+                self.state.run(plan, self._ids, codes.contiguous()[None], self._arena, out)
+        cur.wait_stream(ae.stream)
+        out.record_stream(cur)
+        return out.view(1, 1, -1)
+
+    def __del__(self):
+        if getattr(self, "_graph", None):
+            self.ae.lib.zmi_graph_destroy(self._graph)
+            self._graph = None
+
+
+class _BatchCarrySteps:
+    """DACCarryBatchStreamDecoder's decode_steps on the HIP decoder: the lanes of one plan key, any subset of the
+    pool in any order, are ONE launch sequence (their state is gathered into the dense scratch and scattered back,
+    since the _lanes entry points need one lane stride). Not captured (as _BatchWindowDecoder); the arena grows on
+    demand."""
+
+    def __init__(self, ae: "DACAutoencoder", lanes: int, chunk_frames: int):
+        self.ae, self.chunk = ae, int(chunk_frames)
+        self.state = _CarryState(ae, lanes)
+        self._arena = None
+        self.lane_launches = 0    # launch sequences issued
+        self.lanes_decoded = 0    # lanes decoded in them
+        self.frames_computed = 0  # code frames decoded in them: the frames pushed
+        self.launch_log = []      # (lane ids, n) per launch sequence, the last 64
+
+    def reset(self, lane: int):
+        pass  # an utterance's first push reads no state (ZMI_DAC_MOVE_ZERO)
+
+    def __call__(self, plan, ids, codes) -> list:
+        ae, hop = self.ae, self.state.layout.hop
+        B, m = len(ids), plan.emit1 - plan.emit0
+        ids_t = self.state.lane_ids(ids)
+        cur = torch.cuda.current_stream(ae.dev)
+        ae.stream.wait_stream(cur)
+        with torch.cuda.stream(ae.stream):
+            need = self.state.scratch_halfs(plan, B)[1]
+            if self._arena is None or self._arena.numel() < need:
+                self._arena = None  # freed before the larger one is allocated
+                self._arena = torch.empty(need, dtype=torch.float16, device=ae.dev)
+            out = torch.empty(B, hop * m, dtype=torch.float32, device=ae.dev)
+            self.state.run(plan, ids_t, torch.stack([c.contiguous() for c in codes]), self._arena, out)
+        cur.wait_stream(ae.stream)
+        out.record_stream(cur)
+        self.lane_launches += 1
+        self.lanes_decoded += B
+        self.frames_computed += B * plan.n
+        self.launch_log = (self.launch_log + [(tuple(ids), plan.n)])[-64:]
+        return [out[i].view(1, 1, -1) for i in range(B)]
 
 
 class DACAutoencoder:
@@ -458,18 +707,36 @@ class DACAutoencoder:
         cur.wait_stream(self.stream)
         return out
 
-    def stream_decoder(self, chunk_frames: int = 16, capture: bool | None = None) -> DACStreamDecoder:
+    def carry_layout(self) -> CarryLayout:
+        """The carried-state planner of this decoder's layer list (streaming.CarryLayout)."""
+        if getattr(self, "_carry_layout", None) is None:
+            self._carry_layout = CarryLayout(STRIDES, DILATIONS, DAC_LOOKAHEAD_FRAMES)
+            assert self._carry_layout.hop == DAC_HOP
+        return self._carry_layout
+
+    def stream_decoder(self, chunk_frames: int = 16, capture: bool | None = None, carry: bool = False):
         """An incremental decoder: push() code frames as they become final, flush() at the end; the concatenated
-        returns are bit for bit decode() of all the codes (streaming.py). capture: replay the steady-state window
-        (lookahead + chunk_frames + lookahead frames) as one hipGraph (default: WINDOW_GRAPH)."""
-        win = _WindowDecoder(self, chunk_frames, WINDOW_GRAPH if capture is None else capture)
+        returns are bit for bit decode() of all the codes (streaming.py). capture: replay the steady-state step as
+        one hipGraph (default: WINDOW_GRAPH). carry=False: the window decoder (a window of lookahead + chunk_frames +
+        lookahead frames per chunk_frames emitted). carry=True: the carried-state decoder with the same returns
+        (DACCarryStreamDecoder): every stage keeps its last rows, so a push computes its own frames only."""
+        capture = WINDOW_GRAPH if capture is None else capture
+        if carry:
+            return DACCarryStreamDecoder(_CarryStep(self, chunk_frames, capture), self.carry_layout(), chunk_frames,
+                                         device=self.dev)
+        win = _WindowDecoder(self, chunk_frames, capture)
         return DACStreamDecoder(win, chunk_frames, DAC_LOOKAHEAD_FRAMES, device=self.dev)
 
-    def stream_decoder_batch(self, lanes: int, chunk_frames: int = 16) -> DACBatchStreamDecoder:
+    def stream_decoder_batch(self, lanes: int, chunk_frames: int = 16, carry: bool = False):
         """`lanes` incremental decoders that decode together: push({lane: codes}) / flush(lanes) / reset(lane)
         (streaming.DACBatchStreamDecoder); per lane the concatenated returns are bit for bit decode() of its codes. All
         the windows of equal shape that a call makes due are lanes of one launch sequence (_decode_lanes); stage memory
-        is allocated for the lanes in use."""
+        is allocated for the lanes in use. carry=True: the carried-state decoder with the same returns
+        (DACCarryBatchStreamDecoder): per-lane state, and the lanes of a call whose pushes have one shape (past an
+        utterance's start: equal n) are one launch sequence."""
+        if carry:
+            return DACCarryBatchStreamDecoder(_BatchCarrySteps(self, lanes, chunk_frames), self.carry_layout(), lanes,
+                                              chunk_frames, device=self.dev)
         win = _BatchWindowDecoder(self, lanes, chunk_frames)
         return DACBatchStreamDecoder(win, lanes, chunk_frames, DAC_LOOKAHEAD_FRAMES, device=self.dev)
 

@@ -38,10 +38,18 @@ struct ConvArgs {
   // activation buffers start ls_* elements times l after lane 0's; weights, bias and alpha are shared.
   int lanes = 1;
   size_t ls_x = 0, ls_skip = 0, ls_raw = 0, ls_snake = 0, ls_f32 = 0;
+  // range form of the polyphase ConvTranspose (rng_n > 0, nphase = stride): only output rows rng_n0 .. rng_n0 + rng_n
+  // - 1 of the whole transposed conv, written to out rows 0 .. rng_n - 1; x's row 0 is input row rng_x0. Phase rho
+  // has its own q range (conv_lane_args); n_out as given sizes the grid (the longest phase's rows).
+  int rng_n0 = 0, rng_n = 0, rng_x0 = 0;
 };
 
 // The launch's arguments as this workgroup's lane sees them (its own activation pointers) and its phase rho. A
 // lane is a pointer offset and nothing else: rows outside [0, t_in) are zeros per lane, so no lane reads another's.
+// A phase is in_off = (rho + phase_pad) / out_stride and out_phase = rho. In the range form phase rho computes its
+// q in [qlo, qhi), the rows stride q + rho inside the range: the conv's input offset moves by qlo - rng_x0 and the
+// first row written is stride qlo + rho - rng_n0 (in [0, stride)), so every output row keeps the K order and MFMA
+// chain the whole launch gives it, and nothing outside the range is written.
 __device__ __forceinline__ ConvArgs conv_lane_args(const ConvArgs& a0, int& rho) {
   ConvArgs a = a0;
   rho = blockIdx.z;
@@ -53,6 +61,17 @@ __device__ __forceinline__ ConvArgs conv_lane_args(const ConvArgs& a0, int& rho)
     if (a.out_raw) a.out_raw += l * a.ls_raw;
     if (a.out_snake) a.out_snake += l * a.ls_snake;
     if (a.out_f32) a.out_f32 += l * a.ls_f32;
+  }
+  if (a.nphase > 1) {
+    a.in_off = (rho + a.phase_pad) / a.out_stride;
+    a.out_phase = rho;
+    if (a.rng_n > 0) {
+      const int s = a.out_stride, e = a.rng_n0 + a.rng_n - rho;
+      const int qlo = (max(a.rng_n0 - rho, 0) + s - 1) / s, qhi = e > 0 ? (e + s - 1) / s : 0;
+      a.n_out = max(qhi - qlo, 0);
+      a.in_off += qlo - a.rng_x0;
+      a.out_phase = s * qlo + rho - a.rng_n0;
+    }
   }
   return a;
 }
@@ -315,8 +334,7 @@ __global__ __launch_bounds__(128 * NWN) void conv_kernel(const ConvArgs a0) {
   __shared__ __attribute__((aligned(1024))) char lds_raw[LDS_BYTES];
   const int co_blk = blockIdx.y * BM, q_blk = blockIdx.x * BN;
   const f16_t* const wts = a.w + (size_t)rho * a.w_phase;
-  const int in_off = a.nphase > 1 ? (rho + a.phase_pad) / a.out_stride : a.in_off;
-  const int out_phase = a.nphase > 1 ? rho : a.out_phase;
+  const int in_off = a.in_off, out_phase = a.out_phase;  // this phase's (conv_lane_args)
   const int nci = a.c_in / 32, nsteps = a.taps * nci;
   ConvEpiChan<WM, 128 * NWN> ch;
   ch.load(a, co_blk);
@@ -436,8 +454,7 @@ __global__ __launch_bounds__(512) void conv_stage_kernel(const ConvArgs a0) {
     for (int j = 0; j < WN; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   const int co_blk = blockIdx.y * BM, q_blk = blockIdx.x * BN;
   const f16_t* const wts = a.w + (size_t)rho * a.w_phase;
-  const int in_off = a.nphase > 1 ? (rho + a.phase_pad) / a.out_stride : a.in_off;
-  const int out_phase = a.nphase > 1 ? rho : a.out_phase;
+  const int in_off = a.in_off, out_phase = a.out_phase;  // this phase's (conv_lane_args)
   const int prow = lane >> 2, pchunk = (lane & 3) ^ (((lane >> 4) & 1) << 1);
   const int am = wm * (16 * WM), bn = wn * (16 * WN);
   const int span = (TAPS - 1) * abs(a.tap_step);
@@ -550,8 +567,7 @@ __global__ __launch_bounds__(768) void conv_ldr_kernel(const ConvArgs a0) {
     for (int j = 0; j < WN; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   const int co_blk = blockIdx.y * BM, q_blk = blockIdx.x * BN;
   const f16_t* const wts = a.w + (size_t)rho * a.w_phase;
-  const int in_off = a.nphase > 1 ? (rho + a.phase_pad) / a.out_stride : a.in_off;
-  const int out_phase = a.nphase > 1 ? rho : a.out_phase;
+  const int in_off = a.in_off, out_phase = a.out_phase;  // this phase's (conv_lane_args)
   const int prow = lane >> 2, pchunk = (lane & 3) ^ (((lane >> 4) & 1) << 1);
   const int am = wm * (16 * WM), bn = wn * (16 * WN);
   const int span = (TAPS - 1) * abs(a.tap_step);
@@ -769,7 +785,57 @@ __global__ __launch_bounds__(256) void vq_kernel(const float* lat, int T, const 
   }
 }
 
+// Carried-state streaming decode: the per-lane state pool <-> the dense [lanes][hist | new] scratch of one launch
+// sequence. blockIdx.y: the segment, blockIdx.z: the group's lane (pool lane lane_ids[z], any subset in any order).
+// Offsets and counts in 16-byte units; a lane id outside the pool moves nothing. ZMI_DAC_MOVE_ZERO writes zeros where
+// a gather writes the state (an utterance's first push: the zero state is every stage's zero padding).
+struct MoveArgs {
+  ZmiDacMoveSeg seg[ZMI_DAC_MOVE_SEGS];
+};
+
+__global__ __launch_bounds__(256) void state_move_kernel(uint4* pool, size_t pool_ls, int pool_lanes, uint4* scratch,
+                                                          const int* lane_ids, const MoveArgs m, int mode) {
+  const ZmiDacMoveSeg sg = m.seg[blockIdx.y];
+  const int id = lane_ids[blockIdx.z];
+  if (id < 0 || id >= pool_lanes) return;
+  uint4* const p = pool + (size_t)id * pool_ls + sg.pool_off;
+  uint4* const s = scratch + (size_t)blockIdx.z * sg.scratch_ls + sg.scratch_off;
+  for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < sg.count; i += gridDim.x * 256) {
+    if (mode == ZMI_DAC_MOVE_SCATTER) p[i] = s[i];
+    else s[i] = mode == ZMI_DAC_MOVE_GATHER ? p[i] : uint4{0u, 0u, 0u, 0u};
+  }
+}
+
 }  // namespace
+
+extern "C" int zmi_dac_state_move(void* pool, int64_t pool_lane_units, int pool_lanes, void* scratch,
+                                  int64_t scratch_units, const int* lane_ids, int lanes, const ZmiDacMoveSeg* segs,
+                                  int n_segs, int mode, void* stream) {
+  if (lanes < 0 || lanes > 65535 || n_segs < 0 || n_segs > ZMI_DAC_MOVE_SEGS || pool_lanes < 1 || pool_lane_units < 0 ||
+      scratch_units < 0)
+    return zmi_fail_msg("dac_state_move: 0 <= lanes <= 65535, 0 <= n_segs <= ZMI_DAC_MOVE_SEGS, pool_lanes >= 1");
+  if (mode < ZMI_DAC_MOVE_GATHER || mode > ZMI_DAC_MOVE_ZERO) return zmi_fail_msg("dac_state_move: mode");
+  if (((size_t)pool | (size_t)scratch) & 15) return zmi_fail_msg("dac_state_move: pool and scratch 16-byte aligned");
+  MoveArgs m{};
+  unsigned most = 0;
+  for (int i = 0; i < n_segs; ++i) {
+    const ZmiDacMoveSeg& g = segs[i];
+    if ((uint64_t)g.pool_off + g.count > (uint64_t)pool_lane_units)
+      return zmi_fail_msg("dac_state_move: a segment leaves a lane's state");
+    if (lanes > 1 && g.scratch_ls < g.count) return zmi_fail_msg("dac_state_move: scratch lane stride < count");
+    if (lanes > 0 && (uint64_t)g.scratch_off + (uint64_t)(lanes - 1) * g.scratch_ls + g.count > (uint64_t)scratch_units)
+      return zmi_fail_msg("dac_state_move: a segment leaves the scratch");
+    m.seg[i] = g;
+    most = g.count > most ? g.count : most;
+  }
+  if (lanes == 0 || n_segs == 0 || most == 0) return 0;
+  const unsigned nx = (most + 255) / 256;
+  hipLaunchKernelGGL(state_move_kernel, dim3(nx < 16 ? nx : 16, (unsigned)n_segs, (unsigned)lanes), dim3(256), 0,
+                     (hipStream_t)stream, (uint4*)pool, (size_t)pool_lane_units, pool_lanes, (uint4*)scratch, lane_ids,
+                     m, mode);
+  ZMI_CHECK(hipGetLastError());
+  return 0;
+}
 
 extern "C" int zmi_dac_im2col7(const float* wav, int t, void* col, void* stream) {
   if (t <= 0) return 0;
@@ -1069,6 +1135,34 @@ extern "C" int zmi_dac_conv_t_lanes(const void* x, int t_in, int c_in, const voi
   ConvArgs a{(const f16_t*)x, t_in, c_in, (const f16_t*)w_phases, bias, c_out, 2, -1, 0, t_in, stride, 0,
              stride * t_in, nullptr, (f16_t*)out_raw, (f16_t*)out_snake, alpha, nullptr, 0, stride, pad,
              (size_t)2 * c_out * c_in};
+  int rc = set_lanes(a, lanes, ls_x, 0, ls_raw, ls_snake, 0);
+  if (rc) return rc;
+  rc = launch_conv(a, (hipStream_t)stream);
+  if (rc) return rc;
+  ZMI_CHECK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int zmi_dac_conv_t_range_lanes(const void* x, int x0, int t_in, int c_in, const void* w_phases,
+                                          const float* bias, int c_out, int stride, int pad, int n0, int n,
+                                          void* out_raw, void* out_snake, const float* alpha, int lanes, int64_t ls_x,
+                                          int64_t ls_raw, int64_t ls_snake, void* stream) {
+  // rows n0 .. n0 + n - 1 of zmi_dac_conv_t_lanes, out row 0 = row n0; x row 0 = input row x0 (rows outside the t_in
+  // given are zeros). The range need not be aligned to the stride: phase rho computes q in [ceil((n0 - rho) / stride),
+  // ceil((n0 + n - rho) / stride)) (conv_lane_args), the grid covers the longest phase
+  if (c_in % 32) return zmi_fail_msg("dac_conv_t_range: c_in % 32");
+  if (lanes < 1) return zmi_fail_msg("dac_conv_t_range: lanes >= 1");
+  if (stride < 2 || pad < 0) return zmi_fail_msg("dac_conv_t_range: stride >= 2 (one phase per grid z), pad >= 0");
+  if (n0 < 0 || n < 0 || t_in < 0 || (long)n0 + n > (long)stride * ((long)x0 + t_in) ||
+      std::max((n0 + pad) / stride - 1, 0) < x0)
+    return zmi_fail_msg("dac_conv_t_range: bounds");
+  if (n == 0) return 0;
+  ConvArgs a{(const f16_t*)x, t_in, c_in, (const f16_t*)w_phases, bias, c_out, 2, -1, 0, (n + stride - 1) / stride,
+             stride, 0, n, nullptr, (f16_t*)out_raw, (f16_t*)out_snake, alpha, nullptr, 0, stride, pad,
+             (size_t)2 * c_out * c_in};
+  a.rng_n0 = n0;
+  a.rng_n = n;
+  a.rng_x0 = x0;
   int rc = set_lanes(a, lanes, ls_x, 0, ls_raw, ls_snake, 0);
   if (rc) return rc;
   rc = launch_conv(a, (hipStream_t)stream);

@@ -210,7 +210,7 @@ class Zonos:
     @torch.inference_mode()
     def stream(self, prefix_conditioning: torch.Tensor, audio_prefix_codes: torch.Tensor | None = None,
                max_new_tokens: int = 86 * 30, cfg_scale: float = 2.0, sampling_params: dict = dict(min_p=0.1),
-               chunk_frames: int = 16, sample_rate: int | None = None):
+               chunk_frames: int = 16, sample_rate: int | None = None, decoder: str = "window"):
         """generate() + autoencoder.decode() as a generator of waveform chunks [1, 1, 512 n] fp32 (device): audio
         is yielded while the utterance is still being generated. With the same torch.manual_seed, the chunks
         concatenated are bit for bit decode(generate(...)) (batch 1, generate()'s arguments).
@@ -224,9 +224,14 @@ class Zonos:
         sample_rate (None or 44100: exactly the path above): the chunks leave at that rate, [1, 1, any n > 0], and
         concatenated are bit for bit autoencoder.resample(decode(generate(...)), 44100, sample_rate). A round's
         waveform goes through a streaming resampler (resampling.StreamResampler, zmi_resample) once the round's state
-        copy has shown how much of it counts, so the resampler is never rolled back."""
+        copy has shown how much of it counts, so the resampler is never rolled back.
+
+        decoder: "window" (the default) or "carry", the carried-state DAC decoder (autoencoder.stream_decoder(carry=
+        True)): the same chunks, each decoded at the cost of its own frames; a round's rollback point then holds a
+        copy of the decoder's state."""
         assert cfg_scale != 1, "TODO: add support for cfg_scale=1"
         self._check_not_serving("stream")
+        carry = self._decoder_mode(decoder)
         rate = self._output_rate(sample_rate)
         if prefix_conditioning.shape[0] != 2:
             raise ValueError("stream() has generate()'s batch_size=1 semantics: prefix_conditioning [2, Lc, d]")
@@ -238,9 +243,9 @@ class Zonos:
         e = self.engine
         params = SamplingParams.from_dict(dict(sampling_params), cfg_scale, _draw_seed())
         slot = 0
-        key = (id(self.autoencoder), int(chunk_frames))
+        key = (id(self.autoencoder), int(chunk_frames), carry)
         if key not in self._stream_decoders:  # kept: its window graph and stage buffers serve every later call
-            self._stream_decoders[key] = self.autoencoder.stream_decoder(chunk_frames)
+            self._stream_decoders[key] = self.autoencoder.stream_decoder(chunk_frames, carry=carry)
         dec = self._stream_decoders[key]
         dec._reset()  # (an earlier stream closed before its end)
         rs = None if rate is None else self._stream_resampler(rate, 1)
@@ -384,7 +389,8 @@ class Zonos:
     def stream_batch(self, conds: Sequence[torch.Tensor], prefixes: Sequence[torch.Tensor | None] | None = None,
                      max_new_tokens: Sequence[int] | int = 86 * 30, cfg_scale: float = 2.0,
                      sampling_params: dict = dict(min_p=0.1), seeds: Sequence[int] | None = None,
-                     max_slots: int | None = None, chunk_frames: int = 16, sample_rate: int | None = None):
+                     max_slots: int | None = None, chunk_frames: int = 16, sample_rate: int | None = None,
+                     decoder: str = "window"):
         """generate_batch() + autoencoder.decode() per utterance as a generator of (utterance index, waveform chunk
         [1, 1, 512 n] fp32 (device), last): every utterance's audio is yielded while it and the others are still being
         generated. With the same seeds, utterance i's chunks concatenated are bit for bit
@@ -401,9 +407,14 @@ class Zonos:
 
         sample_rate (None or 44100: exactly the path above): a round's waveforms go through ONE push of a streaming
         resampler over the slots (zmi_resample, on the engine's stream); utterance i's chunks, [1, 1, any n >= 0],
-        concatenated are bit for bit autoencoder.resample(decode(generate_batch(...)[i]), 44100, sample_rate)."""
+        concatenated are bit for bit autoencoder.resample(decode(generate_batch(...)[i]), 44100, sample_rate).
+
+        decoder: "window" (the default) or "carry", the carried-state DAC decoder (autoencoder.stream_decoder_batch(
+        carry=True)): the same items; the slots that push equal frame counts past their start are one launch sequence
+        whatever their positions, and a round decodes the frames it made final, not their windows."""
         assert cfg_scale != 1, "TODO: add support for cfg_scale=1"
         self._check_not_serving("stream_batch")
+        carry = self._decoder_mode(decoder)
         rate = self._output_rate(sample_rate)
         if chunk_frames < 1:
             raise ValueError("chunk_frames >= 1")
@@ -419,10 +430,10 @@ class Zonos:
         slots = min(max_slots or n, n)
         self._ensure_capacity(slots, need_seq, need_pre)
         e, ae = self.engine, self.autoencoder
-        key = (id(ae), int(chunk_frames))
+        key = (id(ae), int(chunk_frames), carry)
         dec = self._stream_batch_decoders.get(key)
         if dec is None or dec.lanes < slots:  # kept: its graphs and stage buffers serve every later call
-            dec = self._stream_batch_decoders[key] = ae.stream_decoder_batch(slots, chunk_frames)
+            dec = self._stream_batch_decoders[key] = ae.stream_decoder_batch(slots, chunk_frames, carry=carry)
         for s in range(slots):
             dec.reset(s)  # (an earlier stream_batch closed before its end)
         queue = sorted(range(n), key=lambda i: -mnt[i])  # longest-processing-time first, so the tail is short
@@ -461,15 +472,23 @@ class Zonos:
                     e.release(s)
 
     def serve(self, max_slots: int, max_seqlen: int, max_prefill: int, chunk_frames: int = 16,
-              pcm16: bool = False, sample_rate: int | None = None) -> ServeSession:
+              pcm16: bool = False, sample_rate: int | None = None, decoder: str = "window") -> ServeSession:
         """A serving session (serving.ServeSession, a context manager): submit() requests from any thread while
         others are being spoken, run_round() from one thread hands out every ticket's chunks, each ticket's
         concatenated bit for bit decode(generate_batch()) of the request alone; with pcm16 they leave as int16 CPU
         tensors (zmi_pcm16_pack); with sample_rate they leave at that rate (zmi_resample between the round's waveforms
-        and the egress; None or 44100: no resampler, the unchanged path). Capacity is fixed here; while the session is
+        and the egress; None or 44100: no resampler, the unchanged path); decoder "window" or "carry" as in
+        stream_batch(). Capacity is fixed here; while the session is
         open generate(), stream(), generate_batch(), stream_batch() and another serve() raise RuntimeError."""
         self._check_not_serving("serve")
-        return ServeSession(self, max_slots, max_seqlen, max_prefill, chunk_frames, pcm16, sample_rate)
+        return ServeSession(self, max_slots, max_seqlen, max_prefill, chunk_frames, pcm16, sample_rate, decoder)
+
+    @staticmethod
+    def _decoder_mode(decoder: str) -> bool:
+        """True for the carried-state DAC decoder, False for the window decoder."""
+        if decoder not in ("window", "carry"):
+            raise ValueError(f'decoder must be "window" or "carry", got {decoder!r}')
+        return decoder == "carry"
 
     def _output_rate(self, sample_rate):
         """None for the decoder's own 44.1 kHz (no resampler), else the validated rate."""

@@ -323,9 +323,10 @@ class ServeSession:
     Every ticket that is not cancelled gets exactly one item with last = True (its chunk may be empty)."""
 
     def __init__(self, model, max_slots: int, max_seqlen: int, max_prefill: int, chunk_frames: int = 16,
-                 pcm16: bool = False, sample_rate: int | None = None):
+                 pcm16: bool = False, sample_rate: int | None = None, decoder: str = "window"):
         if chunk_frames < 1:
             raise ValueError("chunk_frames >= 1")
+        carry = model._decoder_mode(decoder)
         rate = model._output_rate(sample_rate)  # None: 44.1 kHz, the path without a resampler
         if getattr(model, "_serving", None) is not None:
             raise RuntimeError("a serve() session is already open on this model")
@@ -333,10 +334,10 @@ class ServeSession:
         self.sched = SlotScheduler(max_slots, max_seqlen, max_prefill, model.config.backbone.d_model)
         model._ensure_capacity(max_slots, max_seqlen, max_prefill)  # once: a session never rebuilds the engine
         e, ae = model.engine, model.autoencoder
-        key = (id(ae), int(chunk_frames))
+        key = (id(ae), int(chunk_frames), carry)
         dec = model._stream_batch_decoders.get(key)
         if dec is None or dec.lanes < max_slots:  # kept: its graphs and stage buffers serve every later call
-            dec = model._stream_batch_decoders[key] = ae.stream_decoder_batch(max_slots, chunk_frames)
+            dec = model._stream_batch_decoders[key] = ae.stream_decoder_batch(max_slots, chunk_frames, carry=carry)
         for s in range(max_slots):
             dec.reset(s)
         self.dec = dec

@@ -216,4 +216,366 @@ class DACBatchStreamDecoder:
         self._lanes[lane]._reset()
 
 
-__all__ = ["dac_lookahead_frames", "DAC_LOOKAHEAD_FRAMES", "DACStreamDecoder", "DACBatchStreamDecoder", "DAC_HOP"]
+# ----------------------------------------------------------------------------------------------- carried state
+# The incremental form of the same decoder: instead of a halo of R frames on both sides of every chunk, every stage
+# keeps, per lane, the last rows of its input that it has not finished with, and a push of n frames advances every
+# stage from its frontier as far as its input now allows. dac_lookahead_frames' interval arithmetic, run forward:
+#   k7 conv, dilation d:   out row q reads in rows q - 3 d .. q + 3 d   -> frontier f_out = f_in - 3 d
+#   1x1 conv + skip:       pointwise                                    -> the frontier of the k7 before it
+#   ConvTranspose(s, p):   out row n reads in rows (n + p) // s - 1, (n + p) // s
+#                                                                      -> f_out = s f_in - p (not a multiple of s)
+# never below 0 (rows at negative positions are the zero padding: computing them would add the bias), and at the
+# utterance's end every frontier is the stage's whole length (the rows past it are decode()'s right zero padding).
+# A buffer's history is a FIXED number of rows below its frontier (zeros at an utterance's start: the zero state is
+# the zero padding, every buffer holds post-Snake or raw values whose padding is 0): 6 d for a k7's input (its
+# output lags 3 d behind and reads 3 d further back), 3 d for the skip it is added to, 1 for a transposed conv's
+# input, and for the last conv's input what keeps frame recv - R computable.
+
+
+class CarryBuffer:
+    """One activation buffer of the incremental decoder: `rate` rows per code frame, `hist` carried rows; `width`
+    names its channel count ('z', 'c1' or a block index: the planner knows shapes in rows only)."""
+
+    def __init__(self, name: str, rate: int, hist: int, width):
+        self.name, self.rate, self.hist, self.width = name, int(rate), int(hist), width
+
+    def __repr__(self):
+        return f"CarryBuffer({self.name}, rate {self.rate}, hist {self.hist})"
+
+
+class CarryLayout:
+    """The decoder's layer list as a chain of stages over CarryBuffers, and the planner over it.
+
+    stages: dicts with kind 'codes' (from_codes), 'k7' (dilated conv, d), 'pw' (1x1 conv with skip), 'convt'
+    (transposed conv, s, p) or 'out' (the last k7 + tanh); src / dst / skip / raw name buffers. k7_short (a k7 stage's
+    index) and convt_frontier_pad=False build the two wrong plans the tests must reject: one row less history at that
+    stage, and a transposed-conv frontier of s F instead of s F - p."""
+
+    def __init__(self, strides: Sequence[int], dilations: Sequence[int], lookahead: int | None = None,
+                 k7_short: int | None = None, convt_frontier_pad: bool = True):
+        self.strides, self.dilations = tuple(strides), tuple(dilations)
+        self.hop = math.prod(self.strides)
+        self.R = dac_lookahead_frames(strides, dilations) if lookahead is None else int(lookahead)
+        self.convt_frontier_pad = bool(convt_frontier_pad)
+        if not self.strides or not self.dilations:
+            raise ValueError("at least one block and one residual unit")
+        bufs, stages = [], []
+        buf = lambda name, rate, hist, width: bufs.append(CarryBuffer(name, rate, hist, width)) or name  # noqa: E731
+        z = buf("z", 1, 6, "z")
+        stages.append(dict(kind="codes", dst=z))
+        x = buf("a0", 1, 1, "c1")
+        stages.append(dict(kind="k7", d=1, src=z, dst=x))
+        rate = 1
+        for j, s in enumerate(self.strides):
+            rate *= s
+            d0 = self.dilations[0]
+            xu, hu = buf(f"b{j}.x0", rate, 6 * d0, j), buf(f"b{j}.h0", rate, 3 * d0, j)
+            stages.append(dict(kind="convt", s=s, p=math.ceil(s / 2), src=x, dst=xu, raw=hu, block=j))
+            for u, d in enumerate(self.dilations):
+                t = buf(f"b{j}.t{u}", rate, 0, j)
+                stages.append(dict(kind="k7", d=d, src=xu, dst=t, block=j, unit=u))
+                if u + 1 == len(self.dilations):  # the next transposed conv's input, or the last conv's
+                    xn, hn = buf(f"a{j + 1}", rate, 1, j), None
+                else:
+                    dn = self.dilations[u + 1]
+                    xn, hn = buf(f"b{j}.x{u + 1}", rate, 6 * dn, j), buf(f"b{j}.h{u + 1}", rate, 3 * dn, j)
+                stages.append(dict(kind="pw", src=t, skip=hu, dst=xn, raw=hn, block=j, unit=u))
+                xu, hu = xn, hn
+            x = xu
+        stages.append(dict(kind="out", d=1, src=x))
+        self.buffers = {b.name: b for b in bufs}
+        self.stages = stages
+        self.last = x
+        # the last conv emits whole frames, up to frame recv - R: its input's history reaches from that frame's first
+        # sample (less the conv's 3 rows) to the input's frontier, whose lag behind hop * recv is a constant
+        big = 4 * self.R + 64
+        lag = self.hop * big - self._frontiers(big, False)[x]
+        if self.convt_frontier_pad:
+            assert 0 <= lag + 3 <= self.hop * self.R, "the lookahead does not cover the stages' lag"
+        self.buffers[x].hist = max(self.hop * self.R - lag, 0) + 3
+        if k7_short is not None:
+            st = [g for g in stages if g["kind"] in ("k7", "out")][k7_short]
+            self.buffers[st["src"]].hist -= 1
+        self._short = k7_short is not None
+        self._plans: dict = {}
+        r = self.R
+        while min(self._frontiers(r, False).values()) <= 0:
+            r += 1
+        self._steady_from = r
+        self.k7_stages = sum(g["kind"] in ("k7", "out") for g in stages)  # the last conv is a k7 too
+
+    # ------------------------------------------------------------------------------------------ frontiers
+    def _frontiers(self, recv: int, final: bool) -> dict:
+        """{buffer: rows [0, f) valid} with `recv` frames received (final: the utterance is recv frames long)."""
+        f = {}
+        for g in self.stages:
+            k = g["kind"]
+            if k == "codes":
+                f[g["dst"]] = recv
+            elif k == "k7":
+                fi = f[g["src"]]
+                f[g["dst"]] = fi if final else max(fi - 3 * g["d"], 0)
+            elif k == "pw":
+                f[g["dst"]] = f[g["src"]]
+                if g["raw"]:
+                    f[g["raw"]] = f[g["src"]]
+            elif k == "convt":
+                fi = f[g["src"]]
+                fo = g["s"] * fi if final else max(g["s"] * fi - (g["p"] if self.convt_frontier_pad else 0), 0)
+                f[g["dst"]] = fo
+                if g["raw"]:
+                    f[g["raw"]] = fo
+        return f
+
+    def emitted(self, recv: int, final: bool) -> int:
+        """Frames whose samples have been returned once `recv` frames are in: all up to recv - R (at the end: all)."""
+        return recv if final else max(recv - self.R, 0)
+
+    def plan(self, recv: int, n: int, final: bool = False) -> "CarryPlan":
+        """The launch sequence of a push of n more frames after `recv` (final: they end the utterance)."""
+        if recv < 0 or n < 0:
+            raise ValueError("recv >= 0 and n >= 0")
+        return CarryPlan(self, recv, n, final)
+
+    def step_plan(self, recv: int, n: int, final: bool = False) -> "CarryPlan":
+        """plan() for the launch sequence alone, kept: once every stage's frontier has left 0 and frames are being
+        emitted, a push's launches (row counts, offsets into [hist | new], tails: CarryPlan.key) no longer depend on
+        the position, so every later push takes the plan of the first such position (its absolute rows are that
+        position's)."""
+        key = (min(recv, self._steady_from), n, bool(final))
+        plan = self._plans.get(key)
+        if plan is None:
+            plan = self._plans[key] = self.plan(*key).check() if self.convt_frontier_pad and not self._short \
+                else self.plan(*key)
+        return plan
+
+
+class CarryPlan:
+    """What one push computes. Per buffer b: prev[b] / now[b] its frontier before / after, new[b] = now - prev the rows
+    appended, and its scratch is [hist | new] rows whose row 0 is absolute row base[b] = prev[b] - hist. Per stage
+    (self.steps, the layout's stages in order) a dict with
+      out0, n_out     first output row (absolute) and row count (the stage's dst rows prev .. now);
+      lo, hi          absolute input rows read, [lo, hi) (k7: out0 - 3 d .. out0 + n_out + 3 d; convt: (out0 + p) // s - 1
+                      .. (out0 + n_out - 1 + p) // s + 1), of which rows below prev[src] come from the history and the
+                      rest are new; rows at or past now[src] are read only at the utterance's end (zero padding);
+      in_off          the local row of src's scratch that output row 0 reads first (k7: out0 - 3 d - base); skip_off
+                      the same for a 1x1 conv's skip; n0 (convt) the first output row counted from s * base[src], the
+                      transposed conv's row 0 of an input that starts at src's scratch;
+      tail            {buffer: local first row} of the `hist` rows to keep for the next push: rows new .. new + hist.
+    key: the tuple that decides every launch's shape (two pushes of equal key are one launch sequence's lanes)."""
+
+    def __init__(self, lay: CarryLayout, recv: int, n: int, final: bool):
+        self.layout, self.recv, self.n, self.final, self.first = lay, recv, n, bool(final), recv == 0
+        self.prev = lay._frontiers(recv, False)
+        self.now = lay._frontiers(recv + n, final)
+        B = lay.buffers
+        self.new = {b: self.now[b] - self.prev[b] for b in B}
+        self.base = {b: self.prev[b] - B[b].hist for b in B}
+        self.emit0, self.emit1 = lay.emitted(recv, False), lay.emitted(recv + n, final)
+        steps = []
+        for g in lay.stages:
+            k = g["kind"]
+            st = dict(g)
+            if k == "codes":
+                st.update(out0=recv, n_out=n)
+            elif k == "out":
+                src = g["src"]
+                st.update(out0=lay.hop * self.emit0, n_out=lay.hop * (self.emit1 - self.emit0))
+                st.update(lo=st["out0"] - 3, hi=st["out0"] + st["n_out"] + 3, in_off=st["out0"] - 3 - self.base[src])
+            else:
+                dst, src = g["dst"], g["src"]
+                st.update(out0=self.prev[dst], n_out=self.new[dst])
+                if k == "k7":
+                    d = g["d"]
+                    st.update(lo=st["out0"] - 3 * d, hi=st["out0"] + st["n_out"] + 3 * d,
+                              in_off=st["out0"] - 3 * d - self.base[src])
+                elif k == "pw":
+                    st.update(lo=st["out0"], hi=st["out0"] + st["n_out"], in_off=0,
+                              skip_off=st["out0"] - self.base[g["skip"]])
+                else:
+                    s, p = g["s"], g["p"]
+                    st.update(lo=(st["out0"] + p) // s - 1, hi=(st["out0"] + st["n_out"] - 1 + p) // s + 1,
+                              n0=st["out0"] - s * self.base[src])
+            steps.append(st)
+        self.steps = steps
+        self.tail = {b: self.new[b] for b in B if B[b].hist}
+        self.key = (self.first, self.final, tuple((st.get("in_off", 0), st.get("skip_off", 0), st.get("n0", 0),
+                                                   st["n_out"]) for st in steps))
+
+    def rows(self, name: str) -> int:
+        """Rows of a buffer's [hist | new] scratch."""
+        return self.layout.buffers[name].hist + self.new[name]
+
+    def check(self):
+        """Every row a stage reads is in its source's [hist | new] and, unless the utterance ends, below the source's
+        frontier; no row at a negative position is computed."""
+        for st in self.steps:
+            if st["kind"] == "codes" or st["n_out"] == 0:
+                continue
+            assert st["out0"] >= 0, st
+            srcs = [(st["src"], st["lo"], st["hi"])]
+            if st["kind"] == "pw":
+                srcs.append((st["skip"], st["out0"], st["out0"] + st["n_out"]))
+            for b, lo, hi in srcs:
+                assert lo >= self.base[b], (st, b, lo, self.base[b])
+                assert hi <= self.now[b] or self.final, (st, b, hi, self.now[b])
+        return self
+
+
+class DACCarryStreamDecoder:
+    """DACStreamDecoder's surface on the carried-state decoder: push() returns the frames up to recv - R, flush() the
+    rest, concatenated bit for bit decode() of all the codes; a push costs its own frames, not a window's.
+
+    decode_step(plan, codes [9, n] int64) -> [1, 1, hop (emit1 - emit0)] fp32 runs one CarryPlan on the lane's state
+    (DACAutoencoder.stream_decoder(carry=True) supplies the HIP one, the CPU tests a restatement); it has reset() (the
+    state is zero again) and snapshot() / restore(s) (stream()'s rollback of a push past the utterance's end)."""
+
+    def __init__(self, decode_step, layout: CarryLayout, chunk_frames: int = 16, device=None):
+        if chunk_frames < 1:
+            raise ValueError("chunk_frames >= 1")
+        self.decode_step, self.layout = decode_step, layout
+        self.chunk, self.R = int(chunk_frames), layout.R
+        self.device = torch.device(device) if device is not None else torch.device("cpu")
+        self._recv = 0
+
+    frames_received = property(lambda self: self._recv)
+    frames_emitted = property(lambda self: self.layout.emitted(self._recv, False))
+
+    def _reset(self):
+        self._recv = 0
+        self.decode_step.reset()
+
+    def _state(self):
+        return self._recv, (self.decode_step.snapshot() if self._recv else None)
+
+    def _restore(self, state):
+        self._recv, snap = state
+        if snap is None:
+            self.decode_step.reset()
+        else:
+            self.decode_step.restore(snap)
+
+    def _codes(self, codes: torch.Tensor) -> torch.Tensor:
+        if codes.dim() == 3:
+            if codes.shape[0] != 1:
+                raise ValueError("DACCarryStreamDecoder decodes one utterance: codes [1, 9, n] or [9, n]")
+            codes = codes[0]
+        if codes.dim() != 2 or codes.shape[0] != N_CODEBOOKS:
+            raise ValueError(f"codes must be [1, {N_CODEBOOKS}, n] or [{N_CODEBOOKS}, n]")
+        return codes.to(self.device, torch.int64)
+
+    def _run(self, codes: torch.Tensor, final: bool) -> torch.Tensor:
+        """A push goes in pieces of at most chunk_frames (as the window decoder emits chunk_frames at a time): a long
+        one, an audio prefix for instance, takes a chunk's scratch, and its whole chunks the steady-state step."""
+        n = codes.shape[1]
+        if n == 0 and not (final and self._recv):
+            return torch.empty(1, 1, 0, dtype=torch.float32, device=self.device)
+        parts = []
+        for a in range(0, max(n, 1), self.chunk):
+            k = min(self.chunk, n - a)
+            plan = self.layout.step_plan(self._recv, k, final)
+            self._recv += k
+            parts.append(self.decode_step(plan, codes[:, a: a + k]))
+        return parts[0] if len(parts) == 1 else torch.cat(parts, dim=-1)
+
+    @torch.inference_mode()
+    def push(self, codes: torch.Tensor) -> torch.Tensor:
+        """codes [1, 9, n] or [9, n] int64 (n >= 0) -> [1, 1, hop m] fp32: the m frames whose right lookahead is now
+        available (m may be 0)."""
+        return self._run(self._codes(codes), False)
+
+    @torch.inference_mode()
+    def flush(self) -> torch.Tensor:
+        """The utterance has ended: the samples of the frames not yet emitted. The decoder is then ready for a new one."""
+        out = self._run(torch.empty(N_CODEBOOKS, 0, dtype=torch.int64, device=self.device), True)
+        self._reset()
+        return out
+
+
+class DACCarryBatchStreamDecoder:
+    """DACBatchStreamDecoder's surface on the carried-state decoder: `lanes` independent utterances, each with a state
+    of its own; the lanes of a call whose plans have one key (in the steady state: equal n) go to ONE call of
+
+        decode_steps(plan, lane ids, list of codes [9, n] int64) -> list of [1, 1, hop m] fp32
+
+    which also has reset(lane). Per lane the returns are exactly a DACCarryStreamDecoder's for the same pushes."""
+
+    def __init__(self, decode_steps, layout: CarryLayout, lanes: int, chunk_frames: int = 16, device=None):
+        if lanes < 1 or chunk_frames < 1:
+            raise ValueError("lanes >= 1 and chunk_frames >= 1")
+        self.decode_steps, self.layout = decode_steps, layout
+        self.chunk, self.R = int(chunk_frames), layout.R
+        self.device = torch.device(device) if device is not None else torch.device("cpu")
+        self._recv = [0] * int(lanes)
+
+    @property
+    def lanes(self) -> int:
+        return len(self._recv)
+
+    def frames_received(self, lane: int) -> int:
+        return self._recv[lane]
+
+    def frames_emitted(self, lane: int) -> int:
+        return self.layout.emitted(self._recv[lane], False)
+
+    def _run(self, codes: dict, final: bool) -> dict:
+        """Every lane's push in pieces of at most chunk_frames (DACCarryStreamDecoder._run); the lanes' i-th pieces of
+        one plan key are one decode_steps call."""
+        parts = {lane: [] for lane in codes}
+        a = 0
+        while True:
+            groups = {}
+            for lane, c in codes.items():
+                n = c.shape[1]
+                if a >= max(n, 1) or (n == 0 and not (final and self._recv[lane])):
+                    continue
+                k = min(self.chunk, n - a)
+                plan = self.layout.step_plan(self._recv[lane], k, final)
+                g = groups.setdefault(plan.key, (plan, [], []))
+                g[1].append(lane)
+                g[2].append(c[:, a: a + k])
+                self._recv[lane] += k
+            if not groups:
+                break
+            for plan, ids, cs in groups.values():
+                wavs = list(self.decode_steps(plan, ids, cs))
+                if len(wavs) != len(ids):
+                    raise RuntimeError(f"decode_steps returned {len(wavs)} waveforms for {len(ids)} lanes")
+                for lane, w in zip(ids, wavs):
+                    parts[lane].append(w)
+            a += self.chunk
+        empty = torch.empty(1, 1, 0, dtype=torch.float32, device=self.device)
+        return {lane: empty if not p else p[0] if len(p) == 1 else torch.cat(p, dim=-1) for lane, p in parts.items()}
+
+    @torch.inference_mode()
+    def push(self, codes: dict) -> dict:
+        """{lane: codes [9, n] or [1, 9, n] int64} -> {lane: [1, 1, hop m] fp32}: per lane, the m frames whose right
+        lookahead is now available (m may be 0)."""
+        took = {}
+        for lane, c in codes.items():  # every lane's arguments are checked before any lane's state changes
+            if not 0 <= lane < len(self._recv):
+                raise ValueError(f"lane {lane} outside [0, {len(self._recv)})")
+            if c.dim() not in (2, 3) or c.shape[-2] != N_CODEBOOKS or (c.dim() == 3 and c.shape[0] != 1):
+                raise ValueError(f"codes must be [1, {N_CODEBOOKS}, n] or [{N_CODEBOOKS}, n]")
+            took[lane] = (c[0] if c.dim() == 3 else c).to(self.device, torch.int64)
+        return self._run(took, False)
+
+    @torch.inference_mode()
+    def flush(self, lanes) -> dict:
+        """These lanes' utterances have ended: {lane: the samples of its frames not yet emitted}. The lanes are then
+        ready for new utterances."""
+        lanes = list(lanes)
+        empty = torch.empty(N_CODEBOOKS, 0, dtype=torch.int64, device=self.device)
+        out = self._run({lane: empty for lane in lanes}, True)
+        for lane in lanes:
+            self.reset(lane)
+        return out
+
+    def reset(self, lane: int):
+        """Drop a lane's utterance without decoding what is left of it: its state is zero again."""
+        self._recv[lane] = 0
+        self.decode_steps.reset(lane)
+
+
+__all__ = ["dac_lookahead_frames", "DAC_LOOKAHEAD_FRAMES", "DACStreamDecoder", "DACBatchStreamDecoder", "DAC_HOP",
+           "CarryBuffer", "CarryLayout", "CarryPlan", "DACCarryStreamDecoder", "DACCarryBatchStreamDecoder"]
