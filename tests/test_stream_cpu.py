@@ -7,7 +7,8 @@ from tests.stream_cases import CHUNKS, PATTERNS, lengths, pushes, random_codes, 
 
 from oracle.dac_cpu import OracleDAC
 from zonos_vibes_amd import synthetic as syn
-from zonos_vibes_amd.streaming import DAC_LOOKAHEAD_FRAMES, DACStreamDecoder, dac_lookahead_frames
+from zonos_vibes_amd.streaming import (DAC_LOOKAHEAD_FRAMES, CarryLayout, DACStreamDecoder, dac_lookahead_frames,
+                                       dac_stages)
 
 
 @pytest.fixture(scope="module")
@@ -27,6 +28,43 @@ def test_lookahead_toy_layer_list():
     assert dac_lookahead_frames((2,), (1,)) == 7
     # no upsampling, no residual unit: the two k7 convs and the 2-tap transposed conv (k2, s1, p1: x[n], x[n + 1])
     assert dac_lookahead_frames((1,), ()) == 7
+
+
+TOY_NAMES = [f"decoder.{n}" for n in (
+    "conv1.weight", "conv1.bias", "block.0.snake1.alpha", "block.0.conv_t1.weight", "block.0.conv_t1.bias",
+    "block.0.res_unit1.snake1.alpha", "block.0.res_unit1.conv1.weight", "block.0.res_unit1.conv1.bias",
+    "block.0.res_unit1.snake2.alpha", "block.0.res_unit1.conv2.weight", "block.0.res_unit1.conv2.bias",
+    "snake1.alpha", "conv2.weight", "conv2.bias")]
+
+
+@pytest.mark.parametrize("strides, dilations, names", [
+    (syn.DAC_STRIDES, syn.DAC_DILATIONS, [sp.name for sp in syn.dac_specs() if sp.name.startswith("decoder.")]),
+    ((2,), (1,), TOY_NAMES)], ids=["dac", "toy"])
+def test_stage_list(strides, dilations, names):
+    """The one statement of the decoder's launches: their count and order, the state_dict names they carry (every
+    decoder tensor exactly once), the Snake a 1x1 conv's output is stored under, and that CarryLayout walks it."""
+    stages = dac_stages(strides, dilations)
+    kinds = [st["kind"] for st in stages]
+    assert len(stages) == 2 + (1 + 2 * len(dilations)) * len(strides) + 1  # three dilations: 2 + 7 blocks + 1
+    assert len(stages) == 31 or strides != syn.DAC_STRIDES
+    assert kinds == ["codes", "k7"] + (["convt"] + ["k7", "pw"] * len(dilations)) * len(strides) + ["out"]
+    units = [(st["block"], st["unit"]) for st in stages if st["kind"] == "pw"]
+    assert units == [(j, u) for j in range(len(strides)) for u in range(len(dilations))]
+    assert [st["d"] for st in stages if st["kind"] == "k7"] == [1] + list(dilations) * len(strides)
+    assert [(st["s"], st["p"]) for st in stages if st["kind"] == "convt"] == [(s, -(-s // 2)) for s in strides]
+    carried = [st["w"] + end for st in stages if "w" in st for end in (".weight", ".bias")] + \
+        [st["alpha"] for st in stages if "alpha" in st]
+    assert len(carried) == len(set(carried)) and sorted(carried) == sorted(names)
+    assert "w" not in stages[0] and "alpha" not in stages[0] and "alpha" not in stages[-1]
+    for i, st in enumerate(stages):
+        if st["kind"] != "pw":
+            continue
+        reader = stages[i + 1]  # what consumes the unit's output: the next unit's k7, a transposed conv, or conv2
+        snake1 = {"k7": lambda r: r["w"][: -len("conv1")] + "snake1.alpha",
+                  "convt": lambda r: r["w"][: -len("conv_t1")] + "snake1.alpha",
+                  "out": lambda r: r["w"][: -len("conv2")] + "snake1.alpha"}[reader["kind"]](reader)
+        assert st["alpha"] == snake1 and reader["src"] == st["dst"], (st, reader)
+    assert CarryLayout(strides, dilations).stages == stages
 
 
 def test_lookahead_against_the_oracle(oracle):

@@ -252,6 +252,35 @@ def check(rc: int, what: str = "") -> None:
         raise RuntimeError(f"libzonos_hip {what} failed (status {rc}): {msg}")
 
 
+def capture(stream: int, run) -> int:
+    """What run() enqueues on `stream`, captured as a hipGraph: its handle, for zmi_graph_launch / zmi_graph_destroy."""
+    check(lib().zmi_graph_begin(stream), "graph_begin")
+    try:
+        run()
+    finally:
+        g = c_void_p()
+        check(lib().zmi_graph_end(stream, ctypes.byref(g)), "graph_end")
+    return g.value
+
+
+class Graph:
+    """A launch sequence on one stream that is captured the first time it is launched and replayed from then on; the
+    hipGraph goes with the object."""
+
+    def __init__(self, stream: int):
+        self.lib, self.stream, self.handle = lib(), stream, None
+
+    def launch(self, run):
+        if self.handle is None:
+            self.handle = capture(self.stream, run)
+        check(self.lib.zmi_graph_launch(self.handle, 1, self.stream), "graph_launch")
+
+    def __del__(self):
+        if getattr(self, "handle", None):
+            self.lib.zmi_graph_destroy(self.handle)
+            self.handle = None
+
+
 def ptr(t) -> int | None:
     """Device pointer of a torch tensor (None for None)."""
     return None if t is None else t.data_ptr()

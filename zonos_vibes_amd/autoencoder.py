@@ -1,9 +1,11 @@
 """DACAutoencoder with the reference's decode() surface (zonos/autoencoder.py:8-27), on HIP kernels.
 
-The decoder path is on the hot path: quantizer.from_codes + DacDecoder.
-`encode` (voice-clone audio prefix) runs DacEncoder + the residual VQ on the
-same MFMA conv kernel (strided convs in polyphase form) plus a VQ kernel; `preprocess` pads to a
-multiple of 512 samples (resampling needs torchaudio, absent here: only 44.1 kHz input is taken).
+The decoder path is on the hot path: quantizer.from_codes + DacDecoder. Its launches are
+stated once, as streaming.dac_stages; the weights are bound to that list at load, and two host walks run it:
+_decode_lanes (decode() and the window decoders, in four stage buffers reused in place) and _CarryState.run (the
+carried-state decoder, on [hist | new] scratch). `encode` (voice-clone audio prefix) runs
+DacEncoder + the residual VQ on the same MFMA conv kernel (strided convs in polyphase form) plus a VQ kernel;
+`preprocess` resamples to 44.1 kHz on the GPU (zmi_resample, resampling.py) and pads to a multiple of 512 samples.
 
 Weights use transformers' DacModel state_dict names (quantizer.quantizers.{i}.*, decoder.*);
 weight-norm pairs (weight_g / weight_v, or parametrizations.weight.original0 / original1) are
@@ -13,6 +15,7 @@ from __future__ import annotations
 
 import ctypes
 import math
+from types import SimpleNamespace
 
 import torch
 
@@ -21,7 +24,7 @@ from . import synthetic as syn
 from .config import DAC_HOP, DAC_SAMPLE_RATE, N_CODEBOOKS
 from .resampling import GpuResampler, StreamResampler, resample_plan
 from .streaming import (DAC_LOOKAHEAD_FRAMES, CarryLayout, DACBatchStreamDecoder, DACCarryBatchStreamDecoder,  # noqa: F401
-                        DACCarryStreamDecoder, DACStreamDecoder, dac_lookahead_frames)
+                        DACCarryStreamDecoder, DACStreamDecoder, dac_lookahead_frames, dac_stages)
 
 STRIDES = syn.DAC_STRIDES
 ENC_STRIDES = syn.DAC_ENC_STRIDES
@@ -114,64 +117,83 @@ def pack_im2col_conv1(w1: torch.Tensor) -> torch.Tensor:
 # measures both)
 WINDOW_GRAPH = True
 
+STAGE_HALFS_PER_FRAME = 49152  # max over stages of C x time per code frame (blocks 3 and 4: 192 x 256 = 96 x 512)
+
+
+class _Grow:
+    """`count` fp16 device buffers that grow on demand, the old ones freed before the larger ones are allocated."""
+
+    def __init__(self, dev, count: int):
+        self.dev, self.count, self.bufs = dev, count, None
+
+    def __call__(self, halfs: int) -> list:
+        if self.bufs is None or self.bufs[0].numel() < halfs:
+            self.bufs = None
+            self.bufs = [torch.empty(halfs, dtype=torch.float16, device=self.dev) for _ in range(self.count)]
+        return self.bufs
+
+
+class _OnStream:
+    """The stream hand-off: the autoencoder's stream waits for the caller's, the body runs on it, and the caller's
+    stream waits for it. Yields a list: the tensors the body puts there were allocated on the autoencoder's stream and
+    are handed to the caller's (record_stream). (A class: a generator-based context manager costs every replay of a
+    captured window a microsecond more.)"""
+    __slots__ = ("ae", "cur", "ctx", "made")
+
+    def __init__(self, ae: "DACAutoencoder"):
+        self.ae = ae
+
+    def __enter__(self) -> list:
+        self.cur = torch.cuda.current_stream(self.ae.dev)
+        self.ae.stream.wait_stream(self.cur)
+        self.ctx = torch.cuda.stream(self.ae.stream)
+        self.ctx.__enter__()
+        self.made = []
+        return self.made
+
+    def __exit__(self, *exc):
+        self.ctx.__exit__(*exc)
+        if exc[0] is None:
+            self.cur.wait_stream(self.ae.stream)
+            for t in self.made:
+                t.record_stream(self.cur)
+
 
 class _WindowDecoder:
-    """DACStreamDecoder's decode_window on the HIP decoder: a window is decoded by _decode_one's launch sequence in
-    stage buffers of its own (a captured graph keeps their addresses), and the last stage computes only the kept
-    samples (zmi_dac_conv_out_range), so the crop costs no copy of the window and no host sync."""
+    """DACStreamDecoder's decode_window on the HIP decoder: a window is decoded by _decode_lanes' launch sequence at
+    one lane, in stage buffers of its own (a captured graph keeps their addresses), and the last stage computes only
+    the kept samples, so the crop costs no copy of the window and no host sync."""
 
     def __init__(self, ae: "DACAutoencoder", chunk_frames: int, capture: bool):
         self.ae, self.chunk, self.R, self.capture = ae, int(chunk_frames), DAC_LOOKAHEAD_FRAMES, bool(capture)
         self.wmax = 2 * self.R + self.chunk
-        self._bufs = None
+        self._bufs = _Grow(ae.dev, 4)
         self._graph = None
         self.graph_replays = 0
         self.frames_computed = 0  # code frames decoded (a window's halo frames count)
-
-    def _alloc(self):
-        ae = self.ae
-        self._bufs = [torch.empty(49152 * self.wmax, dtype=torch.float16, device=ae.dev) for _ in range(4)]
-        self._gcodes = torch.zeros(N_CODEBOOKS, self.wmax, dtype=torch.int64, device=ae.dev)
-        self._gout = torch.empty(DAC_HOP * self.chunk, dtype=torch.float32, device=ae.dev)
 
     def __call__(self, codes: torch.Tensor, f0: int, f1: int) -> torch.Tensor:
         ae = self.ae
         W = codes.shape[1]
         assert 0 <= f0 < f1 <= W <= self.wmax, (f0, f1, W)
         self.frames_computed += W
-        cur = torch.cuda.current_stream(ae.dev)
-        ae.stream.wait_stream(cur)
-        with torch.cuda.stream(ae.stream):
-            if self._bufs is None:
-                self._alloc()
-            crop = (DAC_HOP * f0, DAC_HOP * (f1 - f0))
+        crop = (DAC_HOP * f0, DAC_HOP * (f1 - f0))
+        with ae.on_stream() as made:
+            bufs = self._bufs(STAGE_HALFS_PER_FRAME * self.wmax)
             if self.capture and W == self.wmax and f0 == self.R and f1 == self.R + self.chunk:
-                self._gcodes.copy_(codes)
                 if self._graph is None:
-                    _lib.check(ae.lib.zmi_graph_begin(ae.sptr), "graph_begin")
-                    try:
-                        ae._decode_one(self._gcodes, self._gout, self._bufs, crop)
-                    finally:
-                        g = ctypes.c_void_p()
-                        _lib.check(ae.lib.zmi_graph_end(ae.sptr, ctypes.byref(g)), "graph_end")
-                    self._graph = g.value
-                _lib.check(ae.lib.zmi_graph_launch(self._graph, 1, ae.sptr), "graph_launch")
+                    self._gcodes = torch.zeros(1, N_CODEBOOKS, self.wmax, dtype=torch.int64, device=ae.dev)
+                    self._gout = torch.empty(1, crop[1], dtype=torch.float32, device=ae.dev)
+                    self._graph = _lib.Graph(ae.sptr)
+                self._gcodes[0].copy_(codes)
+                self._graph.launch(lambda: ae._decode_lanes(self._gcodes, self._gout, bufs, crop))
                 self.graph_replays += 1
                 out = self._gout.clone()
             else:
-                out = torch.empty(crop[1], dtype=torch.float32, device=ae.dev)
-                ae._decode_one(codes.contiguous(), out, self._bufs, crop)
-        cur.wait_stream(ae.stream)
-        out.record_stream(cur)
+                out = torch.empty(1, crop[1], dtype=torch.float32, device=ae.dev)
+                ae._decode_lanes(codes.contiguous()[None], out, bufs, crop)
+            made.append(out)
         return out.view(1, 1, -1)
-
-    def __del__(self):
-        if getattr(self, "_graph", None):
-            self.ae.lib.zmi_graph_destroy(self._graph)
-            self._graph = None
-
-
-STAGE_HALFS_PER_FRAME = 49152  # max over stages of C x time per code frame (blocks 3 and 4: 192 x 256 = 96 x 512)
 
 
 class _BatchWindowDecoder:
@@ -186,51 +208,38 @@ class _BatchWindowDecoder:
         self.ae, self.max_lanes, self.chunk, self.R = ae, int(max_lanes), int(chunk_frames), DAC_LOOKAHEAD_FRAMES
         self.wmax = 2 * self.R + self.chunk
         self.single = _WindowDecoder(ae, chunk_frames, WINDOW_GRAPH)
-        self._cap = 0        # lanes the stage buffers hold
-        self._bufs = None
+        self._bufs = _Grow(ae.dev, 4)
         self.lane_launches = 0  # _decode_lanes launch sequences issued
         self.lanes_decoded = 0  # windows decoded in them
         self.frames_computed = 0  # code frames decoded in them (the single windows count theirs)
 
-    def _reserve(self, lanes: int):
-        if lanes > self._cap:
-            self._bufs = None  # freed before the larger ones are allocated
-            self._bufs = [torch.empty(lanes * STAGE_HALFS_PER_FRAME * self.wmax, dtype=torch.float16, device=self.ae.dev)
-                          for _ in range(4)]
-            self._cap = lanes
-
     def _group(self, windows, W: int, f0: int, f1: int) -> list:
         """One shape's windows (n >= 2) -> their waveforms [1, 1, 512 (f1 - f0)], in order."""
         n = len(windows)
-        self._reserve(n)
         out = torch.empty(n, DAC_HOP * (f1 - f0), dtype=torch.float32, device=self.ae.dev)
-        self.ae._decode_lanes(torch.stack(windows), out, self._bufs, (DAC_HOP * f0, DAC_HOP * (f1 - f0)))
+        self.ae._decode_lanes(torch.stack(windows), out, self._bufs(n * STAGE_HALFS_PER_FRAME * self.wmax),
+                              (DAC_HOP * f0, DAC_HOP * (f1 - f0)))
         self.lane_launches += 1
         self.lanes_decoded += n
         self.frames_computed += n * W
         return [out[i].view(1, 1, -1) for i in range(n)]
 
     def __call__(self, windows: list) -> list:
-        ae = self.ae
         groups: dict = {}
         for i, (codes, f0, f1) in enumerate(windows):
             W = codes.shape[1]
             assert 0 <= f0 < f1 <= W <= self.wmax, (f0, f1, W)
             groups.setdefault((W, f0, f1), []).append(i)
         res = [None] * len(windows)
-        cur = torch.cuda.current_stream(ae.dev)
         for (W, f0, f1), idx in groups.items():
             for k in range(0, len(idx), self.max_lanes):
                 part = idx[k: k + self.max_lanes]
                 if len(part) == 1:
                     res[part[0]] = self.single(windows[part[0]][0], f0, f1)
                     continue
-                ae.stream.wait_stream(cur)
-                with torch.cuda.stream(ae.stream):
-                    outs = self._group([windows[i][0] for i in part], W, f0, f1)
-                cur.wait_stream(ae.stream)
-                for i, o in zip(part, outs):
-                    o.record_stream(cur)
+                with self.ae.on_stream() as made:
+                    made += self._group([windows[i][0] for i in part], W, f0, f1)
+                for i, o in zip(part, made):
                     res[i] = o
         return res
 
@@ -239,7 +248,7 @@ class _CarryState:
     """The carried-state decoder's memory and launch sequence, shared by the single-utterance and the batched step:
     a state pool [lanes][state halfs] fp16 (every CarryBuffer's `hist` rows, 425,856 bytes per lane for the DAC) and
     a scratch arena with one dense [group lanes][hist | new][C] buffer per CarryBuffer, so no stage overwrites
-    another's input: _decode_one's in-place reuse (a unit's 1x1 conv writes over its own k7's input and over the
+    another's input: _decode_lanes' in-place reuse (a unit's 1x1 conv writes over its own k7's input and over the
     skip) would destroy rows the next push needs as history. A run is: gather (or zero, on an utterance's first
     push) the history into the scratch, the decoder's 31 launches on [hist | new] through pointer offsets and in_off
     (zmi_dac_conv_lanes as it is; zmi_dac_conv_t_range_lanes for the transposed convs, whose frontier s F - p is
@@ -248,9 +257,8 @@ class _CarryState:
     def __init__(self, ae: "DACAutoencoder", lanes: int):
         self.ae, self.lanes = ae, int(lanes)
         self.layout = ae.carry_layout()
-        widths = {"z": ae.c1_cin, "c1": ae.c1_cout}
-        widths.update({j: blk["cout"] for j, blk in enumerate(ae.blocks)})
-        self.C = {b.name: widths[b.width] for b in self.layout.buffers.values()}
+        self.C = {name: w.c_out for st, w in zip(self.layout.stages, ae.bound)
+                  for name in (st.get("dst"), st.get("raw")) if name}
         self.pool_off, off = {}, 0
         for b in self.layout.buffers.values():
             if b.hist:
@@ -260,6 +268,7 @@ class _CarryState:
         assert off % 8 == 0 and len(self.pool_off) <= 48
         with torch.cuda.stream(ae.stream):
             self.pool = torch.zeros(self.lanes, off, dtype=torch.float16, device=ae.dev)
+        self._arena = _Grow(ae.dev, 1)
         self._ids: dict = {}
         self._layouts: dict = {}  # (plan key, lanes) -> scratch_halfs
         self._segs: dict = {}     # (plan key, lanes, mode) -> the state-move table
@@ -285,6 +294,10 @@ class _CarryState:
                 tmp = max(tmp, size)
         off.update({name: o for name, b in self.layout.buffers.items() if not b.hist})
         return off, o + tmp
+
+    def arena(self, plan, B: int) -> torch.Tensor:
+        """The kept arena, grown to B lanes of this plan."""
+        return self._arena(self.scratch_halfs(plan, B)[1])[0]
 
     def lane_ids(self, ids) -> torch.Tensor:
         key = tuple(ids)
@@ -312,61 +325,43 @@ class _CarryState:
     def run(self, plan, ids_t: torch.Tensor, codes: torch.Tensor, arena: torch.Tensor, out: torch.Tensor):
         """One CarryPlan over the lanes ids_t (int32, device): codes [B, 9, n] int64 contiguous -> out [B, hop m] fp32;
         on the autoencoder's stream. The state is read unless the plan is an utterance's first and written unless
-        it is its last."""
+        it is its last. Every stage reads and writes [hist | new] scratch: its output goes behind the dst's (and the
+        raw's) history rows."""
         ae, lay = self.ae, self.layout
         B = codes.shape[0]
         off, need = self.scratch_halfs(plan, B)
         assert arena.numel() >= need and codes.is_contiguous() and out.is_contiguous()
-        lib, ck, C = ae.lib, _lib.check, self.C
+        lib, ck, C, s = ae.lib, _lib.check, self.C, ae.sptr
         base = arena.data_ptr()
         P = lambda b, row=0: base + 2 * (off[b] + row * C[b])  # noqa: E731
-        LS = lambda b: plan.rows(b) * C[b]  # noqa: E731
-        hist = lambda b: lay.buffers[b].hist  # noqa: E731
+        LS = lambda b: plan.rows(b) * C[b] if b else 0  # noqa: E731
+        new = lambda b: P(b, lay.buffers[b].hist) if b else None  # noqa: E731
         self._move(plan, ids_t, B, arena, off, 2 if plan.first else 0)
-
-        def conv(st, w, bias, c_in, c_out, taps, alpha, skip=None, raw=None):
-            src, dst, n = st["src"], st["dst"], st["n_out"]
-            ck(lib.zmi_dac_conv_lanes(P(src), plan.rows(src), c_in, w.data_ptr(), bias.data_ptr(), c_out, taps,
-                                      st.get("d", 0), st["in_off"], n, 1, 0, n,
-                                      P(skip, st["skip_off"]) if skip else None, P(raw, hist(raw)) if raw else None,
-                                      P(dst, hist(dst)), alpha.data_ptr(), None, B, LS(src), LS(skip) if skip else 0,
-                                      LS(raw) if raw else 0, LS(dst), 0, ae.sptr), "dac_conv_lanes")
-
-        for st in plan.steps:
-            k, n = st["kind"], st["n_out"]
+        for st, w in zip(plan.steps, ae.bound):
+            k, n, src = st["kind"], st["n_out"], st.get("src")
+            dst, raw, skip = st.get("dst"), st.get("raw"), st.get("skip")
             if n == 0:
                 continue
             if k == "codes":
                 ck(lib.zmi_dac_from_codes_lanes(codes.data_ptr(), n, ae.codebooks.data_ptr(), ae.proj_w.data_ptr(),
-                                                ae.proj_b.data_ptr(), P("z", hist("z")), B, N_CODEBOOKS * n, LS("z"),
-                                                ae.sptr), "from_codes_lanes")
-            elif k == "k7" and "block" not in st:
-                conv(st, ae.c1_w, ae.c1_b, ae.c1_cin, ae.c1_cout, 7, ae.blocks[0]["alpha"])
-            elif k == "k7":
-                ru, c = ae.blocks[st["block"]]["res"][st["unit"]], ae.blocks[st["block"]]["cout"]
-                conv(st, ru["w1"], ru["b1"], c, c, 7, ru["a2"])
-            elif k == "pw":
-                j, u = st["block"], st["unit"]
-                blk = ae.blocks[j]
-                ru, c = blk["res"][u], blk["cout"]
-                if u + 1 < len(DILATIONS):
-                    nxt = blk["res"][u + 1]["a1"]
-                else:
-                    nxt = ae.blocks[j + 1]["alpha"] if j + 1 < len(ae.blocks) else ae.final_alpha
-                conv(st, ru["w2"], ru["b2"], c, c, 1, nxt, skip=st["skip"], raw=st["raw"])
+                                                ae.proj_b.data_ptr(), new(dst), B, N_CODEBOOKS * n, LS(dst), s),
+                   "from_codes_lanes")
             elif k == "convt":
-                blk, src, dst, raw = ae.blocks[st["block"]], st["src"], st["dst"], st["raw"]
-                ck(lib.zmi_dac_conv_t_range_lanes(P(src), 0, plan.rows(src), blk["cin"], blk["wt"].data_ptr(),
-                                                  blk["bt"].data_ptr(), blk["cout"], blk["stride"], blk["pad"], st["n0"],
-                                                  n, P(raw, hist(raw)), P(dst, hist(dst)),
-                                                  blk["res"][0]["a1"].data_ptr(), B, LS(src), LS(raw), LS(dst), ae.sptr),
+                ck(lib.zmi_dac_conv_t_range_lanes(P(src), 0, plan.rows(src), w.c_in, w.w.data_ptr(), w.b.data_ptr(),
+                                                  w.c_out, st["s"], st["p"], st["n0"], n, new(raw), new(dst),
+                                                  w.alpha.data_ptr(), B, LS(src), LS(raw), LS(dst), s),
                    "dac_conv_t_range_lanes")
-            else:
-                src = st["src"]
+            elif k == "out":
                 assert out.shape == (B, n), (out.shape, B, n)
-                ck(lib.zmi_dac_conv_out_range_lanes(P(src), plan.rows(src), C[src], ae.out_w.data_ptr(),
-                                                    ae.out_b.data_ptr(), st["in_off"] + 3, n, out.data_ptr(), B, LS(src),
-                                                    n, ae.sptr), "conv_out_range_lanes")
+                ck(lib.zmi_dac_conv_out_range_lanes(P(src), plan.rows(src), w.c_in, w.w.data_ptr(), w.b.data_ptr(),
+                                                    st["in_off"] + 3, n, out.data_ptr(), B, LS(src), n, s),
+                   "conv_out_range_lanes")
+            else:  # k7, pw
+                ck(lib.zmi_dac_conv_lanes(P(src), plan.rows(src), w.c_in, w.w.data_ptr(), w.b.data_ptr(), w.c_out,
+                                          w.taps, st.get("d", 0), st["in_off"], n, 1, 0, n,
+                                          P(skip, st["skip_off"]) if skip else None, new(raw), new(dst),
+                                          w.alpha.data_ptr(), None, B, LS(src), LS(skip), LS(raw), LS(dst), 0, s),
+                   "dac_conv_lanes")
         if not plan.final:
             self._move(plan, ids_t, B, arena, off, 1)
 
@@ -382,7 +377,6 @@ class _CarryStep:
         lay = self.state.layout
         self.steady = lay.plan(lay.R + 1, self.chunk)
         self._ids = self.state.lane_ids((0,))
-        self._arena = None
         self._graph = None
         self.graph_replays = 0
         self.frames_computed = 0  # code frames decoded: a push's own
@@ -399,45 +393,25 @@ class _CarryStep:
             self.state.pool.copy_(snap)
 
     def __call__(self, plan, codes: torch.Tensor) -> torch.Tensor:
-        ae, hop = self.ae, self.state.layout.hop
-        m = plan.emit1 - plan.emit0
+        ae, state = self.ae, self.state
+        shape = (1, state.layout.hop * (plan.emit1 - plan.emit0))
         self.frames_computed += plan.n
-        cur = torch.cuda.current_stream(ae.dev)
-        ae.stream.wait_stream(cur)
-        with torch.cuda.stream(ae.stream):
+        with ae.on_stream() as made:
             if self.capture and plan.key == self.steady.key:
                 if self._graph is None:
-                    self._garena = torch.empty(self.state.scratch_halfs(plan, 1)[1], dtype=torch.float16, device=ae.dev)
+                    self._garena = torch.empty(state.scratch_halfs(plan, 1)[1], dtype=torch.float16, device=ae.dev)
                     self._gcodes = torch.zeros(1, N_CODEBOOKS, self.chunk, dtype=torch.int64, device=ae.dev)
-                    self._gout = torch.empty(1, hop * m, dtype=torch.float32, device=ae.dev)
-                    self._gcodes[0].copy_(codes)
-                    _lib.check(ae.lib.zmi_graph_begin(ae.sptr), "graph_begin")
-                    try:
-                        self.state.run(plan, self._ids, self._gcodes, self._garena, self._gout)
-                    finally:
-                        g = ctypes.c_void_p()
-                        _lib.check(ae.lib.zmi_graph_end(ae.sptr, ctypes.byref(g)), "graph_end")
-                    self._graph = g.value
-                else:
-                    self._gcodes[0].copy_(codes)
-                _lib.check(ae.lib.zmi_graph_launch(self._graph, 1, ae.sptr), "graph_launch")
+                    self._gout = torch.empty(shape, dtype=torch.float32, device=ae.dev)
+                    self._graph = _lib.Graph(ae.sptr)
+                self._gcodes[0].copy_(codes)
+                self._graph.launch(lambda: state.run(plan, self._ids, self._gcodes, self._garena, self._gout))
                 self.graph_replays += 1
                 out = self._gout.clone()
             else:
-                need = self.state.scratch_halfs(plan, 1)[1]
-                if self._arena is None or self._arena.numel() < need:
-                    self._arena = None
-                    self._arena = torch.empty(need, dtype=torch.float16, device=ae.dev)
-                out = torch.empty(1, hop * m, dtype=torch.float32, device=ae.dev)
-                self.state.run(plan, self._ids, codes.contiguous()[None], self._arena, out)
-        cur.wait_stream(ae.stream)
-        out.record_stream(cur)
+                out = torch.empty(shape, dtype=torch.float32, device=ae.dev)
+                state.run(plan, self._ids, codes.contiguous()[None], state.arena(plan, 1), out)
+            made.append(out)
         return out.view(1, 1, -1)
-
-    def __del__(self):
-        if getattr(self, "_graph", None):
-            self.ae.lib.zmi_graph_destroy(self._graph)
-            self._graph = None
 
 
 class _BatchCarrySteps:
@@ -449,7 +423,6 @@ class _BatchCarrySteps:
     def __init__(self, ae: "DACAutoencoder", lanes: int, chunk_frames: int):
         self.ae, self.chunk = ae, int(chunk_frames)
         self.state = _CarryState(ae, lanes)
-        self._arena = None
         self.lane_launches = 0    # launch sequences issued
         self.lanes_decoded = 0    # lanes decoded in them
         self.frames_computed = 0  # code frames decoded in them: the frames pushed
@@ -459,20 +432,13 @@ class _BatchCarrySteps:
         pass  # an utterance's first push reads no state (ZMI_DAC_MOVE_ZERO)
 
     def __call__(self, plan, ids, codes) -> list:
-        ae, hop = self.ae, self.state.layout.hop
-        B, m = len(ids), plan.emit1 - plan.emit0
-        ids_t = self.state.lane_ids(ids)
-        cur = torch.cuda.current_stream(ae.dev)
-        ae.stream.wait_stream(cur)
-        with torch.cuda.stream(ae.stream):
-            need = self.state.scratch_halfs(plan, B)[1]
-            if self._arena is None or self._arena.numel() < need:
-                self._arena = None  # freed before the larger one is allocated
-                self._arena = torch.empty(need, dtype=torch.float16, device=ae.dev)
-            out = torch.empty(B, hop * m, dtype=torch.float32, device=ae.dev)
-            self.state.run(plan, ids_t, torch.stack([c.contiguous() for c in codes]), self._arena, out)
-        cur.wait_stream(ae.stream)
-        out.record_stream(cur)
+        ae, state = self.ae, self.state
+        B = len(ids)
+        ids_t = state.lane_ids(ids)
+        with ae.on_stream() as made:
+            out = torch.empty(B, state.layout.hop * (plan.emit1 - plan.emit0), dtype=torch.float32, device=ae.dev)
+            state.run(plan, ids_t, torch.stack([c.contiguous() for c in codes]), state.arena(plan, B), out)
+            made.append(out)
         self.lane_launches += 1
         self.lanes_decoded += B
         self.frames_computed += B * plan.n
@@ -500,7 +466,12 @@ class DACAutoencoder:
                                                          sp.scale, sp.offset, 1, self.sptr), "fill")
                     state_dict[sp.name] = t
         self._prepare(_fold_weight_norm(state_dict))
-        self._bufs = None
+        self._bufs = _Grow(self.dev, 4)  # decode() at B = 1
+        self._walks: dict = {}  # (B, T, crop, stage buffers) -> _walk
+
+    def on_stream(self) -> "_OnStream":
+        """`with ae.on_stream() as made:` is the stream hand-off of every entry point (_OnStream)."""
+        return _OnStream(self)
 
     # --------------------------------------------------------------- weight layout
     def _prepare(self, sd: dict):
@@ -515,26 +486,34 @@ class DACAutoencoder:
             self.proj_w = torch.stack([f32(sd[f"{q}{i}.out_proj.weight"]).reshape(-1, 8)
                                        for i in range(N_CODEBOOKS)]).contiguous()
             self.proj_b = torch.stack([f32(sd[f"{q}{i}.out_proj.bias"]) for i in range(N_CODEBOOKS)]).contiguous()
-            self.c1_w, self.c1_b = conv_w(sd["decoder.conv1.weight"]), f32(sd["decoder.conv1.bias"])
-            self.c1_cin, self.c1_cout = sd["decoder.conv1.weight"].shape[1], sd["decoder.conv1.weight"].shape[0]
-            self.blocks = []
-            for j, s in enumerate(STRIDES):
-                p = f"decoder.block.{j}."
-                wt = sd[p + "conv_t1.weight"].to(self.dev, torch.float32)  # [cin][cout][2s]
-                pad = math.ceil(s / 2)
-                blk = dict(stride=s, pad=pad, cin=wt.shape[0], cout=wt.shape[1],
-                           alpha=f32(sd[p + "snake1.alpha"]).reshape(-1),
-                           wt=pack_conv_transpose(wt, s, pad), bt=f32(sd[p + "conv_t1.bias"]), res=[])
-                for u in range(3):
-                    r = p + f"res_unit{u + 1}."
-                    blk["res"].append(dict(a1=f32(sd[r + "snake1.alpha"]).reshape(-1),
-                                           w1=conv_w(sd[r + "conv1.weight"]), b1=f32(sd[r + "conv1.bias"]),
-                                           a2=f32(sd[r + "snake2.alpha"]).reshape(-1),
-                                           w2=conv_w(sd[r + "conv2.weight"]), b2=f32(sd[r + "conv2.bias"])))
-                self.blocks.append(blk)
-            self.final_alpha = f32(sd["decoder.snake1.alpha"]).reshape(-1)
-            self.out_w, self.out_b = pack_conv_out(f32(sd["decoder.conv2.weight"]),   # [1][96][7]
-                                                   f32(sd["decoder.conv2.bias"]))
+            # The decoder's weights, bound to its stages once (streaming.dac_stages names them): per stage the packed
+            # weight, bias, widths, taps and the alpha its output is stored under, and `slots`, its (src, dst, skip,
+            # raw) among the four stage buffers (H, SA, SB, S2) of the whole-utterance walk, which reuses them in
+            # place: the raw skip path in H, the Snake'd activations in SA and SB in turn (a transposed conv reads one
+            # and writes the other), z and a unit's k7 output in S2 (conv1, which reads z there, writes SA).
+            self.stages, self.bound = dac_stages(STRIDES, DILATIONS), []
+            slot, x = {}, 1
+            for st in self.stages:
+                k = st["kind"]
+                if k == "convt":
+                    x = 3 - x
+                if k != "out":
+                    slot[st["dst"]] = 3 if k == "codes" or (k == "k7" and slot[st["src"]] != 3) else x
+                if st.get("raw"):
+                    slot[st["raw"]] = 0
+                slots = tuple(slot.get(st.get(role)) for role in ("src", "dst", "skip", "raw"))
+                if k == "codes":
+                    self.bound.append(SimpleNamespace(c_out=self.proj_b.shape[1], slots=slots))
+                    continue
+                wt, b = sd[st["w"] + ".weight"].to(self.dev, torch.float32), f32(sd[st["w"] + ".bias"])
+                if k == "convt":  # [cin][cout][2s]
+                    c_in, c_out, w = wt.shape[0], wt.shape[1], pack_conv_transpose(wt, st["s"], st["p"])
+                elif k == "out":  # [1][96][7], in zmi_dac_conv_out's 32-channel tile
+                    c_in, c_out, (w, b) = wt.shape[1], 32, pack_conv_out(wt, b)
+                else:
+                    c_in, c_out, w = wt.shape[1], wt.shape[0], pack_conv(wt)
+                self.bound.append(SimpleNamespace(w=w, b=b, c_in=c_in, c_out=c_out, taps=wt.shape[2], slots=slots,
+                                                  alpha=f32(sd[st["alpha"]]).reshape(-1) if "alpha" in st else None))
             self.has_encoder = "encoder.conv1.weight" in sd
             if self.has_encoder:
                 self._prepare_encoder(sd, f32, conv_w)
@@ -568,13 +547,6 @@ class DACAutoencoder:
         self.cb_n = torch.nn.functional.normalize(self.codebooks, dim=-1).contiguous()
         self.cb_n2 = self.cb_n.pow(2).sum(-1).contiguous()
 
-    def _buffers(self, T: int):
-        need = 49152 * T  # max over stages of C x time (blocks 3 and 4: 192 x 256T = 96 x 512T)
-        if self._bufs is None or self._bufs[0].numel() < need:
-            with torch.cuda.stream(self.stream):
-                self._bufs = [torch.empty(need, dtype=torch.float16, device=self.dev) for _ in range(4)]
-        return self._bufs
-
     # --------------------------------------------------------------- decode
     def _conv(self, x, t_in, c_in, w, b, c_out, taps, step, off, n_out, stride, phase, t_out, skip=None, raw=None,
               snake=None, alpha=None, f32=None):
@@ -582,136 +554,88 @@ class DACAutoencoder:
         _lib.check(self.lib.zmi_dac_conv(p(x), t_in, c_in, p(w), p(b), c_out, taps, step, off, n_out, stride, phase,
                                          t_out, p(skip), p(raw), p(snake), p(alpha), p(f32), self.sptr), "dac_conv")
 
-    def _decode_one(self, codes: torch.Tensor, out: torch.Tensor, bufs=None, crop=None):
-        """codes [9, T] int64 (device) -> out [512 T] fp32 (modeling_dac.py:347-371, 407-441).
-        bufs: the four stage buffers (default: the decoder's own, grown to T). crop = (q0, n): only samples
-        q0 .. q0 + n - 1 are computed by the last stage, into out [n] (the streaming decoder's window crop)."""
-        T = codes.shape[-1]
-        H, SA, SB, S2 = self._buffers(T) if bufs is None else bufs
-        z = S2
-        _lib.check(self.lib.zmi_dac_from_codes(codes.data_ptr(), T, self.codebooks.data_ptr(), self.proj_w.data_ptr(),
-                                               self.proj_b.data_ptr(), z.data_ptr(), self.sptr), "from_codes")
-        c = self.c1_cout
-        # conv1 (k7, pad 3) -> Snake of block 0 (its only consumer is block 0's ConvTranspose)
-        self._conv(z, T, self.c1_cin, self.c1_w, self.c1_b, c, 7, 1, -3, T, 1, 0, T, snake=SA,
-                   alpha=self.blocks[0]["alpha"])
-        t = T
-        xin, xalt = SA, SB
-        for j, blk in enumerate(self.blocks):
-            s, cin, cout = blk["stride"], blk["cin"], blk["cout"]
-            tn = t * s
-            res = blk["res"]
-            # ConvTranspose1d(k=2s, s, pad=ceil(s/2)), every phase in one launch
-            _lib.check(self.lib.zmi_dac_conv_t(xin.data_ptr(), t, cin, blk["wt"].data_ptr(), blk["bt"].data_ptr(),
-                                               cout, s, blk["pad"], H.data_ptr(), xalt.data_ptr(),
-                                               res[0]["a1"].data_ptr(), self.sptr), "dac_conv_t")
-            for u, dil in enumerate(DILATIONS):
-                ru = res[u]
-                self._conv(xalt, tn, cout, ru["w1"], ru["b1"], cout, 7, dil, -3 * dil, tn, 1, 0, tn, snake=S2,
-                           alpha=ru["a2"])
-                last_unit = u == len(DILATIONS) - 1
-                if not last_unit:
-                    nxt = res[u + 1]["a1"]
-                elif j + 1 < len(self.blocks):
-                    nxt = self.blocks[j + 1]["alpha"]
-                else:
-                    nxt = self.final_alpha
-                self._conv(S2, tn, cout, ru["w2"], ru["b2"], cout, 1, 0, 0, tn, 1, 0, tn, skip=H,
-                           raw=None if last_unit else H, snake=xalt, alpha=nxt)
-            t = tn
-            xin, xalt = xalt, xin
-        if crop is not None:
-            _lib.check(self.lib.zmi_dac_conv_out_range(xin.data_ptr(), t, self.blocks[-1]["cout"],
-                                                       self.out_w.data_ptr(), self.out_b.data_ptr(), crop[0], crop[1],
-                                                       out.data_ptr(), self.sptr), "conv_out_range")
-            return
-        _lib.check(self.lib.zmi_dac_conv_out(xin.data_ptr(), t, self.blocks[-1]["cout"], self.out_w.data_ptr(),
-                                             self.out_b.data_ptr(), out.data_ptr(), self.sptr), "conv_out")
-
     def _decode_lanes(self, codes: torch.Tensor, out: torch.Tensor, bufs, crop=None):
-        """_decode_one over B utterances of one length in the same 31 launches (the zmi_dac_*_lanes entry points):
+        """The whole-utterance walk of the stage list (modeling_dac.py:347-371, 407-441), over B utterances of one
+        length in its 31 launches (the zmi_dac_*_lanes entry points; B = 1 is what their single forms forward to):
         codes [B, 9, T] int64 contiguous (device) -> out [B, n] fp32 contiguous. bufs: four stage buffers of at least
-        B x 49152 T halfs each; every stage's activations are [B][t][c] dense, so a lane's stride is that stage's
-        t x c. crop = (q0, n): samples q0 .. q0 + n - 1 of every lane (default: all 512 T). Each lane's samples have
-        the bits _decode_one gives them (the lanes entry points' contract, tests/test_gpu_dac_lanes.py)."""
+        B x STAGE_HALFS_PER_FRAME x T halfs each; every stage's activations are [B][t][c] dense, so a lane's stride is
+        that stage's t x c. crop = (q0, n): only samples q0 .. q0 + n - 1 of every lane are computed by the last stage
+        (the streaming decoders' window crop; default: all 512 T). A lane's samples have the same bits at every B
+        (the lanes entry points' contract, tests/test_gpu_dac_lanes.py)."""
         B, _, T = codes.shape
         assert codes.is_contiguous() and out.is_contiguous() and out.shape[0] == B
         assert all(b.numel() >= B * STAGE_HALFS_PER_FRAME * T for b in bufs)
         H, SA, SB, S2 = bufs
-        lib, p, ck = self.lib, _lib.ptr, _lib.check
+        key = (B, T, crop, H.data_ptr(), SA.data_ptr(), SB.data_ptr(), S2.data_ptr())
+        walk = self._walks.get(key)
+        if walk is None:
+            if len(self._walks) >= 256:  # (a stream's first and last windows have shapes of their own; kept small)
+                self._walks.clear()
+            walk = self._walks[key] = self._walk(*key)
+        (_, from_codes, a0), convs, (_, conv_out, a1) = walk
+        assert out.shape[1] == a1[6].value
+        _lib.check(from_codes(codes.data_ptr(), *a0[1:]), "from_codes_lanes")
+        for what, fn, args in convs:
+            _lib.check(fn(*args), what)
+        _lib.check(conv_out(*a1[:7], out.data_ptr(), *a1[8:]), "conv_out_range_lanes")
 
-        def conv(x, t_in, c_in, w, b, c_out, taps, step, off, n_out, skip=None, raw=None, snake=None, alpha=None):
-            ls_in, ls_out = t_in * c_in, n_out * c_out
-            ck(lib.zmi_dac_conv_lanes(p(x), t_in, c_in, p(w), p(b), c_out, taps, step, off, n_out, 1, 0, n_out, p(skip),
-                                      p(raw), p(snake), p(alpha), None, B, ls_in, ls_out, ls_out, ls_out, 0,
-                                      self.sptr), "dac_conv_lanes")
+    def _walk(self, B: int, T: int, crop, *at) -> tuple:
+        """_decode_lanes' launches for one shape in the stage buffers at `at`, each (name, entry point, arguments): the
+        first, the 29 convs between, the last, with the first's codes and the last's out left open (0). The arguments are built once per shape, as ctypes objects: at one lane the
+        25 arguments of a conv launch cost the host more to work out and convert than the launch itself."""
+        lib, s, at, walk, t = self.lib, self.sptr, at + (None,), [], T
 
-        z = S2
-        ck(lib.zmi_dac_from_codes_lanes(codes.data_ptr(), T, self.codebooks.data_ptr(), self.proj_w.data_ptr(),
-                                        self.proj_b.data_ptr(), z.data_ptr(), B, N_CODEBOOKS * T, 1024 * T, self.sptr),
-           "from_codes_lanes")
-        conv(z, T, self.c1_cin, self.c1_w, self.c1_b, self.c1_cout, 7, 1, -3, T, snake=SA,
-             alpha=self.blocks[0]["alpha"])
-        t = T
-        xin, xalt = SA, SB
-        for j, blk in enumerate(self.blocks):
-            s, cin, cout = blk["stride"], blk["cin"], blk["cout"]
-            tn = t * s
-            res = blk["res"]
-            ck(lib.zmi_dac_conv_t_lanes(xin.data_ptr(), t, cin, blk["wt"].data_ptr(), blk["bt"].data_ptr(), cout, s,
-                                        blk["pad"], H.data_ptr(), xalt.data_ptr(), res[0]["a1"].data_ptr(), B,
-                                        t * cin, tn * cout, tn * cout, self.sptr), "dac_conv_t_lanes")
-            for u, dil in enumerate(DILATIONS):
-                ru = res[u]
-                conv(xalt, tn, cout, ru["w1"], ru["b1"], cout, 7, dil, -3 * dil, tn, snake=S2, alpha=ru["a2"])
-                last_unit = u == len(DILATIONS) - 1
-                if not last_unit:
-                    nxt = res[u + 1]["a1"]
-                elif j + 1 < len(self.blocks):
-                    nxt = self.blocks[j + 1]["alpha"]
-                else:
-                    nxt = self.final_alpha
-                conv(S2, tn, cout, ru["w2"], ru["b2"], cout, 1, 0, 0, tn, skip=H, raw=None if last_unit else H,
-                     snake=xalt, alpha=nxt)
-            t = tn
-            xin, xalt = xalt, xin
-        q0, n = (0, t) if crop is None else crop
-        assert out.shape[1] == n
-        ck(lib.zmi_dac_conv_out_range_lanes(xin.data_ptr(), t, self.blocks[-1]["cout"], self.out_w.data_ptr(),
-                                            self.out_b.data_ptr(), q0, n, out.data_ptr(), B,
-                                            t * self.blocks[-1]["cout"], n, self.sptr), "conv_out_range_lanes")
+        def add(name, *args):
+            fn = getattr(lib, "zmi_dac_" + name)
+            walk.append((name, fn, tuple(None if v is None else ty(v) for ty, v in zip(fn.argtypes, args))))
 
-    # stage memory of one decode() launch sequence over several utterances (4 buffers x 49152 T halfs per lane)
+        for st, w in zip(self.stages, self.bound):
+            k, p = st["kind"], _lib.ptr
+            src, dst, skip, raw = (at[-1 if i is None else i] for i in w.slots)
+            if k == "codes":
+                add("from_codes_lanes", 0, T, p(self.codebooks), p(self.proj_w), p(self.proj_b), dst, B, N_CODEBOOKS * T,
+                    w.c_out * T, s)
+            elif k == "convt":  # every phase in one launch
+                tn = t * st["s"]
+                add("conv_t_lanes", src, t, w.c_in, p(w.w), p(w.b), w.c_out, st["s"], st["p"], raw, dst, p(w.alpha), B,
+                    t * w.c_in, tn * w.c_out, tn * w.c_out, s)
+                t = tn
+            elif k == "out":
+                q0, n = (0, t) if crop is None else crop
+                add("conv_out_range_lanes", src, t, w.c_in, p(w.w), p(w.b), q0, n, 0, B, t * w.c_in, n, s)
+            else:  # k7 (padding 3 d), pw (d = 0)
+                d, ls = st.get("d", 0), t * w.c_out
+                add("conv_lanes", src, t, w.c_in, p(w.w), p(w.b), w.c_out, w.taps, d, -3 * d, t, 1, 0, t, skip, raw, dst,
+                    p(w.alpha), None, B, t * w.c_in, ls, ls, ls, 0, s)
+        return walk[0], walk[1:-1], walk[-1]
+
+    # stage memory of one decode() launch sequence over several utterances (4 buffers x STAGE_HALFS_PER_FRAME T halfs
+    # per lane)
     DECODE_LANES_BYTES = 1 << 30
 
     @torch.inference_mode()
     def decode(self, codes: torch.Tensor) -> torch.Tensor:
         """[B, 9, T] codes -> [B, 1, 512 T] fp32 waveform (reference autoencoder.py:25-27). B > 1: the utterances
         share T, so they are lanes of one launch sequence (as many at a time as DECODE_LANES_BYTES of stage memory
-        hold), each with the bits its own decode() gives."""
+        hold), each with the bits its own decode() gives. B = 1 decodes in kept stage buffers that grow on demand."""
         B, nq, T = codes.shape
         assert nq == N_CODEBOOKS
         out = torch.empty(B, 1, DAC_HOP * T, dtype=torch.float32, device=self.dev)
-        cur = torch.cuda.current_stream(self.dev)
-        self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
+        with self.on_stream():
             codes = codes.to(self.dev, torch.int64).contiguous()
-            if B == 1:
-                self._decode_one(codes[0], out[0, 0])
-            elif T > 0:
+            if T > 0:
                 per = max(1, min(B, 4096, self.DECODE_LANES_BYTES // (4 * 2 * STAGE_HALFS_PER_FRAME * T)))
-                bufs = [torch.empty(per * STAGE_HALFS_PER_FRAME * T, dtype=torch.float16, device=self.dev)
-                        for _ in range(4)]
+                bufs = self._bufs(STAGE_HALFS_PER_FRAME * T) if B == 1 else \
+                    [torch.empty(per * STAGE_HALFS_PER_FRAME * T, dtype=torch.float16, device=self.dev) for _ in range(4)]
                 for b in range(0, B, per):
                     self._decode_lanes(codes[b: b + per], out[b: b + per, 0], bufs)
-        cur.wait_stream(self.stream)
         return out
 
     def carry_layout(self) -> CarryLayout:
-        """The carried-state planner of this decoder's layer list (streaming.CarryLayout)."""
+        """The carried-state planner of this decoder's stage list (streaming.CarryLayout)."""
         if getattr(self, "_carry_layout", None) is None:
             self._carry_layout = CarryLayout(STRIDES, DILATIONS, DAC_LOOKAHEAD_FRAMES)
-            assert self._carry_layout.hop == DAC_HOP
+            assert self._carry_layout.hop == DAC_HOP and self._carry_layout.stages == self.stages
         return self._carry_layout
 
     def stream_decoder(self, chunk_frames: int = 16, capture: bool | None = None, carry: bool = False):
@@ -768,12 +692,9 @@ class DACAutoencoder:
         rs = self._resamplers.get(key)
         if rs is None:
             rs = self._resamplers[key] = GpuResampler(self.dev, *key)
-        cur = torch.cuda.current_stream(self.dev)
-        self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
+        with self.on_stream() as made:
             out = rs(wav.to(self.dev))
-        cur.wait_stream(self.stream)
-        out.record_stream(cur)
+            made.append(out)
         return out
 
     def resampler(self, new_rate: int, lanes: int = 1) -> StreamResampler:
@@ -808,10 +729,10 @@ class DACAutoencoder:
                 self._conv(S2, t, c, ru["w2"], ru["b2"], c, 1, 0, 0, t, 1, 0, t, skip=H, raw=None if last else H,
                            snake=SA, alpha=blk["alpha"] if last else res[u + 1]["a1"])
             tn = t // s
-            nxt = self.eblocks[j + 1]["res"][0]["a1"] if j + 1 < len(self.eblocks) else self.e_final_alpha
+            more = j + 1 < len(self.eblocks)
             # strided conv on the polyphase view of SA ([t][c] read as [t/s][s c]): 3 taps, in_off -1
-            self._conv(SA, tn, s * c, blk["w"], blk["b"], 2 * c, 3, 1, -1, tn, 1, 0, tn,
-                       raw=H if j + 1 < len(self.eblocks) else None, snake=S2, alpha=nxt)
+            self._conv(SA, tn, s * c, blk["w"], blk["b"], 2 * c, 3, 1, -1, tn, 1, 0, tn, raw=H if more else None,
+                       snake=S2, alpha=self.eblocks[j + 1]["res"][0]["a1"] if more else self.e_final_alpha)
             SA, S2 = S2, SA
             t = tn
         self._conv(SA, t, self.e2_cin, self.e2_w, self.e2_b, self.e2_cout, 3, 1, -1, t, 1, 0, t, f32=lat)
@@ -825,15 +746,12 @@ class DACAutoencoder:
         assert ch == 1 and n % DAC_HOP == 0, "preprocess() first: mono, length a multiple of 512"
         T = n // DAC_HOP
         out = torch.empty(B, N_CODEBOOKS, T, dtype=torch.int64, device=self.dev)
-        cur = torch.cuda.current_stream(self.dev)
-        self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
+        with self.on_stream():
             wav = wav.to(self.dev, torch.float32).contiguous()
             lat = torch.empty(T, 1024, dtype=torch.float32, device=self.dev)
             for b in range(B):
                 self.encode_latents(wav[b, 0], lat)
                 self.quantize(lat, out[b])
-        cur.wait_stream(self.stream)
         return out
 
     def quantize(self, lat: torch.Tensor, codes: torch.Tensor):

@@ -642,14 +642,8 @@ class HipEngine:
         rows = self._rows(slots)
         key = (rows, form, self._greedy_step(0, rows // 2), steps)
         if key not in self._graphs:
-            _lib.check(self.lib.zmi_graph_begin(self.sptr), "graph_begin")
-            try:
-                for _ in range(steps):
-                    self.enqueue_step(slots=rows // 2, form=form)
-            finally:
-                g = ctypes.c_void_p()
-                _lib.check(self.lib.zmi_graph_end(self.sptr, ctypes.byref(g)), "graph_end")
-            self._graphs[key] = g.value
+            self._graphs[key] = _lib.capture(
+                self.sptr, lambda: [self.enqueue_step(slots=rows // 2, form=form) for _ in range(steps)])
         return self._graphs[key]
 
     def _advance(self, n: int, slots: int):

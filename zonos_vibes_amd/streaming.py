@@ -18,11 +18,55 @@ from . import synthetic as syn
 from .config import DAC_HOP, N_CODEBOOKS
 
 
+def _snake1(strides, dilations, j: int, u: int) -> str:
+    """The Snake alpha in front of residual unit u of block j; past the block's last unit, in front of what follows the
+    block (the next block's transposed conv, or decoder.conv2). An activation is stored under the Snake of what
+    reads it, so this is the alpha a stage's output is stored under."""
+    if u < len(dilations):
+        return f"decoder.block.{j}.res_unit{u + 1}.snake1.alpha"
+    return f"decoder.block.{j + 1}.snake1.alpha" if j + 1 < len(strides) else "decoder.snake1.alpha"
+
+
+def dac_stages(strides: Sequence[int], dilations: Sequence[int]) -> list:
+    """The DAC decoder's launches (quantizer.from_codes + DacDecoder, modeling_dac.py:347-371, 407-441), stated once:
+    one dict per launch, in order. Everything that runs or reasons about the decoder walks this list: decode() and
+    the window decoders (DACAutoencoder._decode_lanes), the carried-state decoder (CarryLayout / CarryPlan,
+    autoencoder._CarryState.run) and dac_lookahead_frames.
+
+    kind: 'codes' (from_codes), 'k7' (conv of 7 taps at dilation d, padding 3 d: decoder.conv1 and a residual unit's
+    first conv), 'convt' (ConvTranspose1d(k = 2 s, stride s, padding p = ceil(s / 2))), 'pw' (a unit's 1x1 conv plus
+    the skip) or 'out' (decoder.conv2, k7, + tanh); block / unit where it belongs to one. src / dst / skip / raw name
+    its activation buffers: dst holds the output under the Snake `alpha` (a DacModel state_dict key: the Snake of what
+    reads it), raw the same rows before the Snake (the skip of the unit that follows; None where nothing follows in the
+    block). `w` is the state_dict prefix of its .weight and .bias."""
+    strides, dilations = tuple(strides), tuple(dilations)
+    U = len(dilations)
+    before = lambda j, u: (f"b{j}.x{u}", f"b{j}.h{u}") if u < U else (f"a{j + 1}", None)  # noqa: E731  (Snake'd, raw)
+    stages = [dict(kind="codes", dst="z"),
+              dict(kind="k7", d=1, src="z", dst="a0", w="decoder.conv1", alpha=_snake1(strides, dilations, -1, U))]
+    x = "a0"
+    for j, s in enumerate(strides):
+        xu, hu = before(j, 0)
+        stages.append(dict(kind="convt", s=s, p=math.ceil(s / 2), src=x, dst=xu, raw=hu, block=j,
+                           w=f"decoder.block.{j}.conv_t1", alpha=_snake1(strides, dilations, j, 0)))
+        for u, d in enumerate(dilations):
+            unit, t = f"decoder.block.{j}.res_unit{u + 1}.", f"b{j}.t{u}"
+            stages.append(dict(kind="k7", d=d, src=xu, dst=t, block=j, unit=u, w=unit + "conv1",
+                               alpha=unit + "snake2.alpha"))
+            xn, hn = before(j, u + 1)
+            nxt = _snake1(strides, dilations, j, u + 1)
+            stages.append(dict(kind="pw", src=t, skip=hu, dst=xn, raw=hn, block=j, unit=u, w=unit + "conv2", alpha=nxt))
+            xu, hu = xn, hn
+        x = xu
+    stages.append(dict(kind="out", d=1, src=x, w="decoder.conv2"))
+    return stages
+
+
 def dac_lookahead_frames(strides: Sequence[int], dilations: Sequence[int]) -> int:
     """Frames of context the DAC decoder needs on either side of a frame (DacDecoder, modeling_dac.py:407-441).
 
-    Walks the layer list backward from the output samples [0, hop) of frame 0, keeping the first and last index
-    they depend on at each layer's input rate:
+    Walks the stage list backward from the output samples [0, hop) of frame 0, keeping the first and last index
+    they depend on at each stage's input rate:
       Conv1d k7, dilation d, padding 3 d (the final conv, a residual unit's first conv, conv1): [lo - 3 d, hi + 3 d];
       the residual units' 1x1 convs and the Snakes: pointwise;
       ConvTranspose1d(k = 2 s, stride s, padding p = ceil(s / 2)): out[n] = sum_i x[i] w[n + p - i s] over
@@ -31,17 +75,38 @@ def dac_lookahead_frames(strides: Sequence[int], dilations: Sequence[int]) -> in
     is periodic in the hop), and the lookahead is the larger side.
     """
     lo, hi = 0, math.prod(strides) - 1
-    lo, hi = lo - 3, hi + 3                      # decoder.conv2 (k7)
-    for s in reversed(list(strides)):
-        for d in dilations:                      # three residual units: k7 at dilation d, then 1x1
-            lo, hi = lo - 3 * d, hi + 3 * d
-        p = math.ceil(s / 2)
-        lo, hi = (lo + p) // s - 1, (hi + p) // s
-    lo, hi = lo - 3, hi + 3                      # decoder.conv1 (k7)
+    for g in reversed(dac_stages(strides, dilations)):
+        if g["kind"] in ("k7", "out"):
+            lo, hi = lo - 3 * g["d"], hi + 3 * g["d"]
+        elif g["kind"] == "convt":
+            lo, hi = (lo + g["p"]) // g["s"] - 1, (hi + g["p"]) // g["s"]
     return max(-lo, hi)
 
 
 DAC_LOOKAHEAD_FRAMES = dac_lookahead_frames(syn.DAC_STRIDES, syn.DAC_DILATIONS)
+
+
+def _codes_2d(codes: torch.Tensor) -> torch.Tensor:
+    """One utterance's pushed codes, [1, 9, n] or [9, n], as [9, n]."""
+    if codes.dim() not in (2, 3) or codes.shape[-2] != N_CODEBOOKS or (codes.dim() == 3 and codes.shape[0] != 1):
+        raise ValueError(f"codes must be [1, {N_CODEBOOKS}, n] or [{N_CODEBOOKS}, n]")
+    return codes[0] if codes.dim() == 3 else codes
+
+
+def _lane_codes(codes: dict, lanes: int) -> dict:
+    """A batched push's {lane: codes} as {lane: [9, n]}: every lane's arguments are checked before any lane's state
+    changes."""
+    for lane in codes:
+        if not 0 <= lane < lanes:
+            raise ValueError(f"lane {lane} outside [0, {lanes})")
+    return {lane: _codes_2d(c) for lane, c in codes.items()}
+
+
+def _join(parts: list, device) -> torch.Tensor:
+    """The waveforms of one call, joined: [1, 1, samples] (no parts: an empty waveform)."""
+    if not parts:
+        return torch.empty(1, 1, 0, dtype=torch.float32, device=device)
+    return parts[0] if len(parts) == 1 else torch.cat(parts, dim=-1)
 
 
 class DACStreamDecoder:
@@ -108,24 +173,14 @@ class DACStreamDecoder:
                 self._held = self._held[:, keep - self._base:]
                 self._base = keep
 
-    def _join(self, parts) -> torch.Tensor:
-        if not parts:
-            return torch.empty(1, 1, 0, dtype=torch.float32, device=self.device)
-        return parts[0] if len(parts) == 1 else torch.cat(parts, dim=-1)
-
     def _run(self, upto: int) -> torch.Tensor:
         parts = [self.decode_window(w, f0, f1) for w, f0, f1 in self._plan(upto)]
         self._advance(upto)
-        return self._join(parts)
+        return _join(parts, self.device)
 
     def _take(self, codes: torch.Tensor) -> int:
         """Append pushed codes; returns the frame up to which samples can now be emitted."""
-        if codes.dim() == 3:
-            if codes.shape[0] != 1:
-                raise ValueError("DACStreamDecoder decodes one utterance: codes [1, 9, n] or [9, n]")
-            codes = codes[0]
-        if codes.dim() != 2 or codes.shape[0] != N_CODEBOOKS:
-            raise ValueError(f"codes must be [1, {N_CODEBOOKS}, n] or [{N_CODEBOOKS}, n]")
+        codes = _codes_2d(codes)
         if codes.shape[1]:
             codes = codes.to(self.device, torch.int64)
             self._held = codes if self._held is None or self._held.shape[1] == 0 else torch.cat([self._held, codes], 1)
@@ -186,7 +241,7 @@ class DACBatchStreamDecoder:
         for lane, plan in plans.items():
             dec = self._lanes[lane]
             dec._advance(upto[lane])
-            out[lane] = dec._join(wavs[i: i + len(plan)])
+            out[lane] = _join(wavs[i: i + len(plan)], self.device)
             i += len(plan)
         return out
 
@@ -194,11 +249,7 @@ class DACBatchStreamDecoder:
     def push(self, codes: dict) -> dict:
         """{lane: codes [9, n] or [1, 9, n] int64} -> {lane: [1, 1, 512 m] fp32}: per lane, the m frames whose right
         lookahead is now available (m may be 0)."""
-        for lane, c in codes.items():  # every lane's arguments are checked before any lane's state changes
-            if not 0 <= lane < len(self._lanes):
-                raise ValueError(f"lane {lane} outside [0, {len(self._lanes)})")
-            if c.dim() not in (2, 3) or c.shape[-2] != N_CODEBOOKS or (c.dim() == 3 and c.shape[0] != 1):
-                raise ValueError(f"codes must be [1, {N_CODEBOOKS}, n] or [{N_CODEBOOKS}, n]")
+        codes = _lane_codes(codes, len(self._lanes))
         return self._run({lane: self._lanes[lane]._take(c) for lane, c in codes.items()})
 
     @torch.inference_mode()
@@ -244,12 +295,10 @@ class CarryBuffer:
 
 
 class CarryLayout:
-    """The decoder's layer list as a chain of stages over CarryBuffers, and the planner over it.
+    """The decoder's stage list (dac_stages) with a CarryBuffer for every buffer it names, and the planner over it.
 
-    stages: dicts with kind 'codes' (from_codes), 'k7' (dilated conv, d), 'pw' (1x1 conv with skip), 'convt'
-    (transposed conv, s, p) or 'out' (the last k7 + tanh); src / dst / skip / raw name buffers. k7_short (a k7 stage's
-    index) and convt_frontier_pad=False build the two wrong plans the tests must reject: one row less history at that
-    stage, and a transposed-conv frontier of s F instead of s F - p."""
+    k7_short (a k7 stage's index) and convt_frontier_pad=False build the two wrong plans the tests must reject: one
+    row less history at that stage, and a transposed-conv frontier of s F instead of s F - p."""
 
     def __init__(self, strides: Sequence[int], dilations: Sequence[int], lookahead: int | None = None,
                  k7_short: int | None = None, convt_frontier_pad: bool = True):
@@ -259,33 +308,23 @@ class CarryLayout:
         self.convt_frontier_pad = bool(convt_frontier_pad)
         if not self.strides or not self.dilations:
             raise ValueError("at least one block and one residual unit")
-        bufs, stages = [], []
-        buf = lambda name, rate, hist, width: bufs.append(CarryBuffer(name, rate, hist, width)) or name  # noqa: E731
-        z = buf("z", 1, 6, "z")
-        stages.append(dict(kind="codes", dst=z))
-        x = buf("a0", 1, 1, "c1")
-        stages.append(dict(kind="k7", d=1, src=z, dst=x))
-        rate = 1
-        for j, s in enumerate(self.strides):
-            rate *= s
-            d0 = self.dilations[0]
-            xu, hu = buf(f"b{j}.x0", rate, 6 * d0, j), buf(f"b{j}.h0", rate, 3 * d0, j)
-            stages.append(dict(kind="convt", s=s, p=math.ceil(s / 2), src=x, dst=xu, raw=hu, block=j))
-            for u, d in enumerate(self.dilations):
-                t = buf(f"b{j}.t{u}", rate, 0, j)
-                stages.append(dict(kind="k7", d=d, src=xu, dst=t, block=j, unit=u))
-                if u + 1 == len(self.dilations):  # the next transposed conv's input, or the last conv's
-                    xn, hn = buf(f"a{j + 1}", rate, 1, j), None
-                else:
-                    dn = self.dilations[u + 1]
-                    xn, hn = buf(f"b{j}.x{u + 1}", rate, 6 * dn, j), buf(f"b{j}.h{u + 1}", rate, 3 * dn, j)
-                stages.append(dict(kind="pw", src=t, skip=hu, dst=xn, raw=hn, block=j, unit=u))
-                xu, hu = xn, hn
-            x = xu
-        stages.append(dict(kind="out", d=1, src=x))
-        self.buffers = {b.name: b for b in bufs}
-        self.stages = stages
-        self.last = x
+        self.stages = stages = dac_stages(strides, dilations)
+        # every stage's outputs as buffers at its rate, each with the history its reader needs (above)
+        self.buffers, rate = {}, 1
+        for g in stages:
+            k = g["kind"]
+            if k in ("k7", "out"):
+                d = g["d"]
+                self.buffers[g["src"]].hist = 6 * d
+            elif k == "convt":
+                self.buffers[g["src"]].hist = 1
+                rate *= g["s"]
+            elif k == "pw":
+                self.buffers[g["skip"]].hist = 3 * d  # the dilation of the unit's k7
+            for name in (g.get("dst"), g.get("raw")):
+                if name:
+                    self.buffers[name] = CarryBuffer(name, rate, 0, "z" if k == "codes" else g.get("block", "c1"))
+        self.last = x = stages[-1]["src"]
         # the last conv emits whole frames, up to frame recv - R: its input's history reaches from that frame's first
         # sample (less the conv's 3 rows) to the input's frontier, whose lag behind hop * recv is a constant
         big = 4 * self.R + 64
@@ -422,74 +461,58 @@ class CarryPlan:
         return self
 
 
+class _OneLane:
+    """A single lane's decode_step as the decode_steps of a one-lane DACCarryBatchStreamDecoder."""
+
+    def __init__(self, decode_step):
+        self.decode_step = decode_step
+
+    def __call__(self, plan, ids, codes) -> list:
+        return [self.decode_step(plan, codes[0])]
+
+    def reset(self, lane: int):
+        self.decode_step.reset()
+
+
 class DACCarryStreamDecoder:
     """DACStreamDecoder's surface on the carried-state decoder: push() returns the frames up to recv - R, flush() the
-    rest, concatenated bit for bit decode() of all the codes; a push costs its own frames, not a window's.
+    rest, concatenated bit for bit decode() of all the codes; a push costs its own frames, not a window's. It is the
+    one-lane case of DACCarryBatchStreamDecoder.
 
     decode_step(plan, codes [9, n] int64) -> [1, 1, hop (emit1 - emit0)] fp32 runs one CarryPlan on the lane's state
     (DACAutoencoder.stream_decoder(carry=True) supplies the HIP one, the CPU tests a restatement); it has reset() (the
     state is zero again) and snapshot() / restore(s) (stream()'s rollback of a push past the utterance's end)."""
 
     def __init__(self, decode_step, layout: CarryLayout, chunk_frames: int = 16, device=None):
-        if chunk_frames < 1:
-            raise ValueError("chunk_frames >= 1")
+        self._lane = DACCarryBatchStreamDecoder(_OneLane(decode_step), layout, 1, chunk_frames, device)
         self.decode_step, self.layout = decode_step, layout
-        self.chunk, self.R = int(chunk_frames), layout.R
-        self.device = torch.device(device) if device is not None else torch.device("cpu")
-        self._recv = 0
+        self.chunk, self.R, self.device = self._lane.chunk, self._lane.R, self._lane.device
 
-    frames_received = property(lambda self: self._recv)
-    frames_emitted = property(lambda self: self.layout.emitted(self._recv, False))
+    frames_received = property(lambda self: self._lane.frames_received(0))
+    frames_emitted = property(lambda self: self._lane.frames_emitted(0))
 
     def _reset(self):
-        self._recv = 0
-        self.decode_step.reset()
+        self._lane.reset(0)
 
     def _state(self):
-        return self._recv, (self.decode_step.snapshot() if self._recv else None)
+        recv = self.frames_received
+        return recv, (self.decode_step.snapshot() if recv else None)
 
     def _restore(self, state):
-        self._recv, snap = state
+        self._lane._recv[0], snap = state
         if snap is None:
             self.decode_step.reset()
         else:
             self.decode_step.restore(snap)
 
-    def _codes(self, codes: torch.Tensor) -> torch.Tensor:
-        if codes.dim() == 3:
-            if codes.shape[0] != 1:
-                raise ValueError("DACCarryStreamDecoder decodes one utterance: codes [1, 9, n] or [9, n]")
-            codes = codes[0]
-        if codes.dim() != 2 or codes.shape[0] != N_CODEBOOKS:
-            raise ValueError(f"codes must be [1, {N_CODEBOOKS}, n] or [{N_CODEBOOKS}, n]")
-        return codes.to(self.device, torch.int64)
-
-    def _run(self, codes: torch.Tensor, final: bool) -> torch.Tensor:
-        """A push goes in pieces of at most chunk_frames (as the window decoder emits chunk_frames at a time): a long
-        one, an audio prefix for instance, takes a chunk's scratch, and its whole chunks the steady-state step."""
-        n = codes.shape[1]
-        if n == 0 and not (final and self._recv):
-            return torch.empty(1, 1, 0, dtype=torch.float32, device=self.device)
-        parts = []
-        for a in range(0, max(n, 1), self.chunk):
-            k = min(self.chunk, n - a)
-            plan = self.layout.step_plan(self._recv, k, final)
-            self._recv += k
-            parts.append(self.decode_step(plan, codes[:, a: a + k]))
-        return parts[0] if len(parts) == 1 else torch.cat(parts, dim=-1)
-
-    @torch.inference_mode()
     def push(self, codes: torch.Tensor) -> torch.Tensor:
         """codes [1, 9, n] or [9, n] int64 (n >= 0) -> [1, 1, hop m] fp32: the m frames whose right lookahead is now
         available (m may be 0)."""
-        return self._run(self._codes(codes), False)
+        return self._lane.push({0: codes})[0]
 
-    @torch.inference_mode()
     def flush(self) -> torch.Tensor:
         """The utterance has ended: the samples of the frames not yet emitted. The decoder is then ready for a new one."""
-        out = self._run(torch.empty(N_CODEBOOKS, 0, dtype=torch.int64, device=self.device), True)
-        self._reset()
-        return out
+        return self._lane.flush([0])[0]
 
 
 class DACCarryBatchStreamDecoder:
@@ -519,8 +542,9 @@ class DACCarryBatchStreamDecoder:
         return self.layout.emitted(self._recv[lane], False)
 
     def _run(self, codes: dict, final: bool) -> dict:
-        """Every lane's push in pieces of at most chunk_frames (DACCarryStreamDecoder._run); the lanes' i-th pieces of
-        one plan key are one decode_steps call."""
+        """A push goes in pieces of at most chunk_frames (as the window decoder emits chunk_frames at a time): a long
+        one, an audio prefix for instance, takes a chunk's scratch, and its whole chunks the steady-state step. The
+        lanes' i-th pieces of one plan key are one decode_steps call."""
         parts = {lane: [] for lane in codes}
         a = 0
         while True:
@@ -544,21 +568,14 @@ class DACCarryBatchStreamDecoder:
                 for lane, w in zip(ids, wavs):
                     parts[lane].append(w)
             a += self.chunk
-        empty = torch.empty(1, 1, 0, dtype=torch.float32, device=self.device)
-        return {lane: empty if not p else p[0] if len(p) == 1 else torch.cat(p, dim=-1) for lane, p in parts.items()}
+        return {lane: _join(p, self.device) for lane, p in parts.items()}
 
     @torch.inference_mode()
     def push(self, codes: dict) -> dict:
         """{lane: codes [9, n] or [1, 9, n] int64} -> {lane: [1, 1, hop m] fp32}: per lane, the m frames whose right
         lookahead is now available (m may be 0)."""
-        took = {}
-        for lane, c in codes.items():  # every lane's arguments are checked before any lane's state changes
-            if not 0 <= lane < len(self._recv):
-                raise ValueError(f"lane {lane} outside [0, {len(self._recv)})")
-            if c.dim() not in (2, 3) or c.shape[-2] != N_CODEBOOKS or (c.dim() == 3 and c.shape[0] != 1):
-                raise ValueError(f"codes must be [1, {N_CODEBOOKS}, n] or [{N_CODEBOOKS}, n]")
-            took[lane] = (c[0] if c.dim() == 3 else c).to(self.device, torch.int64)
-        return self._run(took, False)
+        codes = _lane_codes(codes, len(self._recv))
+        return self._run({lane: c.to(self.device, torch.int64) for lane, c in codes.items()}, False)
 
     @torch.inference_mode()
     def flush(self, lanes) -> dict:
@@ -577,5 +594,5 @@ class DACCarryBatchStreamDecoder:
         self.decode_steps.reset(lane)
 
 
-__all__ = ["dac_lookahead_frames", "DAC_LOOKAHEAD_FRAMES", "DACStreamDecoder", "DACBatchStreamDecoder", "DAC_HOP",
-           "CarryBuffer", "CarryLayout", "CarryPlan", "DACCarryStreamDecoder", "DACCarryBatchStreamDecoder"]
+__all__ = ["dac_stages", "dac_lookahead_frames", "DAC_LOOKAHEAD_FRAMES", "DACStreamDecoder", "DACBatchStreamDecoder",
+           "DAC_HOP", "CarryBuffer", "CarryLayout", "CarryPlan", "DACCarryStreamDecoder", "DACCarryBatchStreamDecoder"]
