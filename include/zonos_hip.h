@@ -189,6 +189,25 @@ int zmi_attention_pf(const void* q, int ldq, const void* k_cache, const void* v_
 int64_t zmi_attention_work_bytes(int n_query, int hq, int hkv, int hd, int max_pos);
 int64_t zmi_attention_partial_floats(int n_query, int hq, int hkv, int hd, int max_pos);
 int zmi_attention_chunk(void);
+/* Causal prefill attention: many query positions per sequence in one launch, QT = zmi_attention_prefill_queries(hq,
+ * hkv) = 16 / (hq / hkv) consecutive positions sharing every K / V tile they read (hq / hkv in {1, 2, 4}; -1
+ * otherwise). Sequence i owns rows q_row0 .. q_row0 + len - 1 of q and out; they sit at positions pos0 .. pos0 +
+ * len - 1 of KV-cache row kv_row, and the row at position p attends keys 0 .. p of that cache row (caches as for
+ * zmi_attention, already written for those positions). One workgroup per (tile, kv head); `tiles` lists the tiles
+ * in dispatch order, most keys first: {seq, off} = positions pos0 + off .. pos0 + min(off + QT, len) - 1 of sequence
+ * seq, off a multiple of QT, every sequence covered exactly once, so n_tiles = sum of ceil(len / QT).
+ * seqs and tiles are device arrays; seqs_host is the host copy of seqs, which the call checks before it launches
+ * (len >= 0, pos0 + len <= smax, no negative row, n_tiles as above). n_seq == 0 or every len == 0: nothing is
+ * launched. No work or partial buffers, no hand-off between workgroups. Every out row holds the bits
+ * zmi_attention_variant gives for the same (kv_row, position); only rows of a sequence are written.
+ * V is zeroed past each TILE's last position, not each row's: a non-finite V at a later position of the same tile
+ * reaches the tile's earlier rows (it poisons every later row in any form). */
+typedef struct ZmiAttnSeq { int q_row0, len, kv_row, pos0; } ZmiAttnSeq;
+typedef struct ZmiAttnTile { int seq, off; } ZmiAttnTile;
+int zmi_attention_prefill(const void* q, int ldq, const void* k_cache, const void* v_cache, const ZmiAttnSeq* seqs,
+                          int n_seq, int64_t n_tiles, const ZmiAttnTile* tiles, const ZmiAttnSeq* seqs_host, int hq,
+                          int hkv, int hd, int smax, void* out, int ldo, void* stream);
+int zmi_attention_prefill_queries(int hq, int hkv);
 
 /* ---------------------------------------------------------------------------------------
  * Sampler + EOS state machine + delay-pattern frame write, per utterance slot.

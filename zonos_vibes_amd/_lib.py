@@ -138,6 +138,9 @@ _SIGS = {
     "zmi_attention_work_bytes": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
     "zmi_attention_partial_floats": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
     "zmi_attention_chunk": (c_int, []),
+    "zmi_attention_prefill": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p,
+                                      c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "zmi_attention_prefill_queries": (c_int, [c_int, c_int]),
     "zmi_sample_step": (c_int, [ctypes.POINTER(Slots), c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                 c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "zmi_sample_step_greedy": (c_int, [ctypes.POINTER(Slots), c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,

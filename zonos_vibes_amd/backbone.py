@@ -67,7 +67,8 @@ class HipZonosBackbone:
         if lengths is None:
             lengths = torch.full((b,), inference_params.seqlen_offset, dtype=torch.int32, device=self.device)
         # K / V are written (and RoPE'd) at lengths_per_sample + arange(S) (_torch.py:74-77): bound those
-        l_max, l_min = (int(v) for v in torch.stack([lengths.max(), lengths.min()]).tolist())
+        starts = [int(v) for v in lengths.tolist()]  # (one host read: the bounds and the attention's sequence table)
+        l_max, l_min = max(starts), min(starts)
         max_pos = max(l_max, inference_params.seqlen_offset) + s - 1
         if l_min < 0:
             raise ValueError("negative lengths_per_sample")
@@ -83,7 +84,7 @@ class HipZonosBackbone:
                                                                                 device=self.device).view(1, s)
             e.row_pos_pre[:m] = pos.reshape(m)
             e.row_kv_pre[:m] = torch.arange(b, dtype=torch.int32, device=self.device).repeat_interleave(s)
-            e._prefill_layers(m, max_pos)
+            e._prefill_layers(m, max_pos, [(i * s, s, i, starts[i]) for i in range(b)])
             out = torch.empty(m, d, dtype=torch.bfloat16, device=self.device)
             e.final_norm_pre(m, out)
         torch.cuda.current_stream(self.device).wait_stream(e.stream)

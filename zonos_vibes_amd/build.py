@@ -13,7 +13,7 @@ REPO = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(REPO, "include")
 LIB = os.path.join(HERE, "libzonos_hip.so")
-SOURCES = ["zmi_gemv.hip"] + [f"zmi_gemv_e{i}.hip" for i in range(6)] + ["zmi_attn.hip", "zmi_attnblk.hip", "zmi_sample.hip",
+SOURCES = ["zmi_gemv.hip"] + [f"zmi_gemv_e{i}.hip" for i in range(6)] + ["zmi_attn.hip", "zmi_attn_prefill.hip", "zmi_attnblk.hip", "zmi_sample.hip",
                                                                         "zmi_dac.hip", "zmi_misc.hip", "zmi_cond.hip",
                                                                         "zmi_mamba.hip", "zmi_mambablk.hip",
                                                                         "zmi_gemm_splitk.hip", "zmi_spk.hip", "zmi_pcm.hip",

@@ -223,16 +223,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(G == 4 ? 6 :
 
   // ---- e = exp(s - M_j), l = sum e (fp32), P = bf16(e) ----
   for (int g = wave; g < G; g += NWC) {
-    const float M = mj[g];
-    float l = 0.f;
-#pragma unroll
-    for (int i = 0; i < CH / 64; ++i) {
-      const int kk = lane + 64 * i;
-      const float e = kk < nkeys ? expf(sc[g][kk] - M) : 0.f;
-      l += e;
-      pb[g][kk] = (bf16_t)f2bf(e);
-    }
-    l = wave_sum(l);
+    const float l = exp_chunk(sc[g], pb[g], mj[g], nkeys, lane);
     if (lane == 0) lj[g] = l;
   }
   __syncthreads();
@@ -244,22 +235,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(G == 4 ? 6 :
     uint4 pf = uint4{0u, 0u, 0u, 0u};
     if (c16 < G) pf = *reinterpret_cast<const uint4*>(&pb[c16][wave * 32 + 8 * h4]);
     const int kbase = wave * 32 + 8 * h4;  // first key of this lane's 8 positions
-    if (kbase + 8 > nkeys) {
-#pragma unroll
-      for (int dt = 0; dt < 8; ++dt) {
-        uint32_t w[4] = {vf[dt].x, vf[dt].y, vf[dt].z, vf[dt].w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const uint32_t lo = kbase + 2 * e < nkeys ? 0x0000ffffu : 0u;
-          const uint32_t hi = kbase + 2 * e + 1 < nkeys ? 0xffff0000u : 0u;
-          w[e] &= lo | hi;
-        }
-        vf[dt] = uint4{w[0], w[1], w[2], w[3]};
-      }
-    }
 #pragma unroll
     for (int dt = 0; dt < 8; ++dt) {
-      const f32x4_t o = mfma16(pf, vf[dt], f32x4_t{0.f, 0.f, 0.f, 0.f});
+      const f32x4_t o = mfma16(pf, v_keep(vf[dt], kbase, nkeys), f32x4_t{0.f, 0.f, 0.f, 0.f});
       if (h4 == 0) {  // column = dim 16 dt + c16, row = head i
 #pragma unroll
         for (int i = 0; i < G; ++i) opart[wave][i][16 * dt + c16] = o[i];
@@ -471,16 +449,7 @@ __global__ __launch_bounds__(BNT) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
   // ---- e = exp(s - M_j), l per (chunk, head) as the chunked kernel's wave does it, P = bf16(e) ----
   for (int task = wave; task < CPB * G; task += BNW) {
     const int cc = task / G, g = task - cc * G;
-    const float M = mj[g];
-    float l = 0.f;
-#pragma unroll
-    for (int i = 0; i < CH / 64; ++i) {
-      const int kk = cc * CH + lane + 64 * i;
-      const float e = kk < nkeys ? expf(sc[g][kk] - M) : 0.f;
-      l += e;
-      pb[g][kk] = (bf16_t)f2bf(e);
-    }
-    l = wave_sum(l);
+    const float l = exp_chunk(&sc[g][cc * CH], &pb[g][cc * CH], mj[g], nkeys - cc * CH, lane);
     if (lane == 0) lch[cc][g] = l;
   }
   __syncthreads();
@@ -494,18 +463,7 @@ __global__ __launch_bounds__(BNT) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
     const int kbase = 32 * tl + 8 * h4;
 #pragma unroll
     for (int dt = 0; dt < 8; ++dt) {
-      uint4 v = vf[k][dt];
-      if (kbase + 8 > nkeys) {
-        uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const uint32_t lo = kbase + 2 * e < nkeys ? 0x0000ffffu : 0u;
-          const uint32_t hi = kbase + 2 * e + 1 < nkeys ? 0xffff0000u : 0u;
-          w[e] &= lo | hi;
-        }
-        v = uint4{w[0], w[1], w[2], w[3]};
-      }
-      const f32x4_t o = mfma16(pf, v, f32x4_t{0.f, 0.f, 0.f, 0.f});
+      const f32x4_t o = mfma16(pf, v_keep(vf[k][dt], kbase, nkeys), f32x4_t{0.f, 0.f, 0.f, 0.f});
       if (h4 == 0) {
 #pragma unroll
         for (int i = 0; i < G; ++i) opart[tl][i][16 * dt + c16] = o[i];
@@ -561,15 +519,7 @@ __global__ __launch_bounds__(BNT) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
     for (int b = 0; b < nb; ++b) {
       const float ob = ou[(size_t)b * G * HD + e];
       const float2 lm = ld2(lu + (size_t)b * G * 2 + 2 * g);
-      if (b == 0) {
-        acc = ob;
-        l = lm.x;
-      } else {
-        const float et = expf(mprev - lm.y);
-        l = lm.x + et * l;
-        acc = acc * et + ob;
-      }
-      mprev = lm.y;
+      fold_block(acc, l, mprev, ob, lm.x, lm.y, b == 0);
     }
     dst[e] = (bf16_t)f2bf(acc * (1.0f / l));
   }

@@ -127,4 +127,50 @@ __device__ __forceinline__ float2 merge2(const float* o, const float* lm, int nc
 // Chunks of the query at position pos (pos < 0: inactive row, 0 chunks).
 __device__ __forceinline__ int chunks_of(int pos) { return pos < 0 ? 0 : pos / CH + 1; }
 
+// ---- per-element steps every form built on 32-key tiles shares (the chunked kernel, the block form and the
+// causal prefill kernel of zmi_attn_prefill.hip): one statement of each, so the forms cannot drift apart ----
+
+// e = exp(s - M), l and P = bf16(e) of one (chunk, query head), run by one wave: s and p point at the chunk's CH
+// scores / probabilities of that head, nk = the head's keys in the chunk (<= 0: none). Lane L takes keys L and
+// L + 64; returns l = wave_sum(e[L] + e[L + 64]) in every lane.
+__device__ __forceinline__ float exp_chunk(const float* s, bf16_t* p, float M, int nk, int lane) {
+  float l = 0.f;
+#pragma unroll
+  for (int i = 0; i < CH / 64; ++i) {
+    const int kk = lane + 64 * i;
+    const float e = kk < nk ? expf(s[kk] - M) : 0.f;
+    l += e;
+    p[kk] = (bf16_t)f2bf(e);
+  }
+  return wave_sum(l);
+}
+
+// A V^T fragment (8 positions kbase .. kbase + 7 of one dim) with the positions >= nkeys zeroed: stale cache
+// bytes past the bound never enter a product.
+__device__ __forceinline__ uint4 v_keep(const uint4& v, int kbase, int nkeys) {
+  if (kbase + 8 <= nkeys) return v;
+  uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const uint32_t lo = kbase + 2 * e < nkeys ? 0x0000ffffu : 0u;
+    const uint32_t hi = kbase + 2 * e + 1 < nkeys ? 0xffff0000u : 0u;
+    w[e] &= lo | hi;
+  }
+  return uint4{w[0], w[1], w[2], w[3]};
+}
+
+// One step of the block recursion for one (head, dim): block sums ob / lb and running maximum mb of block b
+// folded into acc / l (mprev = the maximum after block b - 1; first: b == 0).
+__device__ __forceinline__ void fold_block(float& acc, float& l, float& mprev, float ob, float lb, float mb, bool first) {
+  if (first) {
+    acc = ob;
+    l = lb;
+  } else {
+    const float et = expf(mprev - mb);
+    l = lb + et * l;
+    acc = acc * et + ob;
+  }
+  mprev = mb;
+}
+
 }  // namespace zmi_attn

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib, quant
+from .prefill_table import PREFILL_ATTN, prefill_table
 from . import synthetic as syn
 from .config import EMB_VOCAB, HEAD_VOCAB, N_CODEBOOKS, ROPE_TABLE_LEN, ZonosConfig
 
@@ -139,6 +140,14 @@ class HipEngine:
         self.attn_variant = 0  # zmi_attention_variant kernel choice (0 = library; all give identical bits)
         # decode QKV + attention as ONE launch (zmi_attn_block) where it applies: <= `attn_block_rows` rows
         # and positions below the fused forms' reach; identical bits either way (speed only)
+        # the prefill's attention: "tiles" (zmi_attention_prefill: 16 / G consecutive positions of a sequence share
+        # each K / V tile, one workgroup walks a tile's 512-key blocks) or "rows" (zmi_attention_pf with one query
+        # per row, the decode kernels); identical bits (tests/test_gpu_attn_prefill.py), so settable at any time.
+        # "tiles" at every row count: the 26 layers' attention alone takes 309 against 882 us at C2 (2 x 161 rows),
+        # 1.01 against 3.44 ms at C5 (2 x 591), 12.8 against 50.7 ms with a 30 s prefix (2 x 2745), 18.3 against
+        # 83.5 ms for an admission of 64 C3 requests; whole prefills 0.88 / 0.81 / 0.56 / 0.81 of "rows"
+        # (device-event times, spreads under 1 %: profiles/prefill_attn_bench.json)
+        self.prefill_attn = "tiles"
         self.attn_block = True
         self.attn_block_slices = 8
         # fused forms tried in order, each where every row's position is below its reach: "split" (one
@@ -734,7 +743,7 @@ class HipEngine:
         self.stream.wait_stream(torch.cuda.current_stream(self.dev))
         with torch.cuda.stream(self.stream):
             self._prefill_stage(slot, cond, prefix, max_new_tokens, params, 0, s_len)
-            self._prefill_layers(2 * s_len, s_len - 1)
+            self._prefill_layers(2 * s_len, s_len - 1, self._slot_seqs(slot, 0, s_len))
             self._prefill_finish(slot, max_new_tokens, 0, s_len, p, noise)
         return s_len
 
@@ -762,7 +771,8 @@ class HipEngine:
                 for (slot, cond, prefix, mnt, params), s_len, off in g:
                     self._prefill_stage(slot, cond, prefix, mnt, params, off, s_len)
                 m = g[-1][2] + 2 * g[-1][1]
-                self._prefill_layers(m, max(s_len for _, s_len, _ in g) - 1)
+                self._prefill_layers(m, max(s_len for _, s_len, _ in g) - 1,
+                                     [sq for it, s_len, off in g for sq in self._slot_seqs(it[0], off, s_len)])
                 for (slot, cond, prefix, mnt, params), s_len, off in g:
                     self._prefill_finish(slot, mnt, off, s_len, s_len - cond.shape[1] - 1, None)
         return lens
@@ -793,9 +803,41 @@ class HipEngine:
         _lib.check(self.lib.zmi_layernorm_rows(self.x_pre.data_ptr(), self.d, m, self.d, ln[0].data_ptr(),
                                                ln[1].data_ptr(), self.eps, out.data_ptr(), self.d, self.sptr), "ln")
 
-    def _prefill_layers(self, m: int, max_pos: int):
+    @staticmethod
+    def _slot_seqs(slot: int, off: int, s_len: int) -> list:
+        """The slot's two prefill sequences (cond, uncond) as ZmiAttnSeq rows (q_row0, len, kv_row, pos0): s_len rows
+        each from row `off` of the prefill buffers, KV rows 2 slot and 2 slot + 1, from position 0."""
+        return [(off, s_len, 2 * slot, 0), (off + s_len, s_len, 2 * slot + 1, 0)]
+
+    def _prefill_table(self, seqs):
+        """The device and host tables of zmi_attention_prefill for one pass (None under prefill_attn = "rows"):
+        built and copied once, used by every layer's launch."""
+        if self.prefill_attn not in PREFILL_ATTN:
+            raise ValueError(f"prefill_attn={self.prefill_attn!r}: expected one of {PREFILL_ATTN}")
+        if self.prefill_attn == "rows":
+            return None
+        sa, tiles = prefill_table(seqs, self.lib.zmi_attention_prefill_queries(self.H, self.Hkv))
+        dev = torch.from_numpy(np.concatenate([sa.ravel(), tiles.ravel()])).to(self.dev)
+        return dev, sa, len(tiles)
+
+    def _prefill_attention(self, i, q, m, row_kv, row_pos, max_pos, out, table):
+        """Causal attention of the m prefill rows over KV layer i: the tiled kernel with the pass's table, or one
+        query per row."""
+        if table is None:
+            self._attention(i, q, m, row_kv, row_pos, max_pos, out)
+            return
+        dev, sa, n_tiles = table
+        qd = self.H * self.hd
+        _lib.check(self.lib.zmi_attention_prefill(
+            q.data_ptr(), qd, self.kc[i].data_ptr(), self.vc[i].data_ptr(), dev.data_ptr(), len(sa), n_tiles,
+            dev.data_ptr() + sa.nbytes, sa.ctypes.data, self.H, self.Hkv, self.hd, self.smax, out.data_ptr(), qd,
+            self.sptr), "attention_prefill")
+
+    def _prefill_layers(self, m: int, max_pos: int, seqs):
         """The m = 2 x S prefill rows through every layer, with the decode step's kernels (same per-row
-        arithmetic; each LayerNorm computed once per layer by zmi_layernorm_rows, identical bits)."""
+        arithmetic; each LayerNorm computed once per layer by zmi_layernorm_rows, identical bits). seqs: the
+        rows' sequences as ZmiAttnSeq rows (q_row0, len, kv_row, pos0), for the tiled attention."""
+        table = self._prefill_table(seqs)
         d, qd = self.d, self.H * self.hd
         qkv_n = (self.H + 2 * self.Hkv) * self.hd
         xn = self.xn_pre
@@ -803,7 +845,7 @@ class HipEngine:
             self._ln_pre(m, (lw["ln1_w"], lw["ln1_b"]), xn)
             self._run_gemv(self._gemv(lw["qkv"], xn, m, qkv_n, d, _lib.EPI_QKV, self.q_pre, qd,
                                       kv=(self.kc[i], self.vc[i]), row_kv=self.row_kv_pre, row_pos=self.row_pos_pre))
-            self._attention(i, self.q_pre, m, self.row_kv_pre, self.row_pos_pre, max_pos, self.attn_pre)
+            self._prefill_attention(i, self.q_pre, m, self.row_kv_pre, self.row_pos_pre, max_pos, self.attn_pre, table)
             self._run_gemv(self._gemv(lw["out"], self.attn_pre, m, d, qd, _lib.EPI_RESIDUAL, self.x_pre, d))
             self._ln_pre(m, (lw["ln2_w"], lw["ln2_b"]), xn)
             self._run_gemv(self._gemv(lw["fc1"], xn, m, 2 * self.F, d, _lib.EPI_SWIGLU, self.h_pre, self.F))

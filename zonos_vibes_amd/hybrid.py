@@ -236,7 +236,7 @@ class HybridEngine(HipEngine):
         return run
 
     def _layer_items(self, lw, m, x, hid, nrm, zx, yb, yn, hm, q, attn, row_kv, row_pos, first, seq_len=None,
-                     max_pos=None):
+                     max_pos=None, table=None):
         """Launches of one block over m rows (decode: seq_len None; prefill: sequences of seq_len rows)."""
         d, md, qd = self.d, self.md, self.H * self.hd
         items = [("call", self._addln(None if first else hid, x, (lw["ln1_w"], lw["ln1_b"]), nrm, m))]
@@ -248,7 +248,8 @@ class HybridEngine(HipEngine):
             if seq_len is None:
                 items.append(("attn", j))
             else:
-                items.append(("call", lambda j=j: self._attention(j, q, m, row_kv, row_pos, max_pos, attn)))
+                items.append(("call", lambda j=j: self._prefill_attention(j, q, m, row_kv, row_pos, max_pos, attn,
+                                                                           table)))
             items.append(("gemv", self._gemv(lw["out"], attn, m, d, qd, _lib.EPI_STORE, hid, d)))
         else:
             items.append(("gemv", self._gemv(lw["in_proj"], nrm, m, md["d_in_proj"], d, _lib.EPI_STORE, zx,
@@ -358,17 +359,19 @@ class HybridEngine(HipEngine):
         return self._plans[(rows, form)]
 
     # ------------------------------------------------------------------ prefill
-    def _prefill_layers(self, m: int, max_pos: int):
+    def _prefill_layers(self, m: int, max_pos: int, seqs):
         """m rows = sequences of max_pos + 1 rows each, every sequence from position 0 (Mamba2.forward
-        from an empty cache; the reference's step() takes one token at a time after that)."""
+        from an empty cache; the reference's step() takes one token at a time after that). seqs: those sequences
+        as ZmiAttnSeq rows, for the MHA layers' tiled attention (HipEngine._prefill_table)."""
         seq_len = max_pos + 1
         if m % seq_len:
             raise ValueError("hybrid prefill: rows must be whole sequences starting at position 0")
+        table = self._prefill_table(seqs)
         for i, lw in enumerate(self.w["layers"]):
             for kind, item in self._layer_items(lw, m, self.x_pre, self.hid_pre, self.nrm_pre, self.zx_pre,
                                                 self.yb_pre, self.yn_pre, self.hm_pre, self.q_pre, self.attn_pre,
                                                 self.row_kv_pre, self.row_pos_pre, first=(i == 0), seq_len=seq_len,
-                                                max_pos=max_pos):
+                                                max_pos=max_pos, table=table):
                 if kind == "gemv":
                     self._run_gemv(item)
                 else:
