@@ -85,6 +85,20 @@ typedef struct ZmiGemvArgs {
 int zmi_pack_weight(const void* src, void* dst, int n_src, int k, int n_pad, int mode, void* stream);
 /* One kernel for every M: a row's result is bit-identical whatever the batch it is computed in. */
 int zmi_gemv_launch(const ZmiGemvArgs* args, int epi, void* stream);
+/* The launch form zmi_gemv_launch(args, epi) would take, computed by the code it dispatches on; launches nothing and
+ * reads no pointer's target (host only: callable without a GPU). kind: the gemv_body kernel, or the K = 2048 many-row
+ * form on M8 or dense-pair MFMAs (ZMI_OPT_GEMM_ROWS); (G, W, NL, RT): column groups per workgroup, waves per group,
+ * 1 KiB weight chunks per lane, rows per tile; ntw: 1 = the single-tile instantiation (M <= RT), 0 = the tile loop;
+ * pro: the resolved prologue (0 plain, 1 LayerNorm, else ZMI_PRO_*); the grid: n_cb column blocks x n_rt row tiles,
+ * rpw row tiles per workgroup. Returns non-zero (zmi_last_error) exactly where zmi_gemv_launch refuses the arguments. */
+enum { ZMI_FORM_BODY = 0, ZMI_FORM_ROWS = 1, ZMI_FORM_ROWS_DENSE = 2 };
+typedef struct ZmiGemvForm {
+  int kind;             /* ZMI_FORM_*                                                          */
+  int G, W, NL, RT;
+  int ntw, pro;
+  int n_cb, n_rt, rpw;
+} ZmiGemvForm;
+int zmi_gemv_form(const ZmiGemvArgs* args, int epi, ZmiGemvForm* out);
 /* Many-row fc2 (K = 8192) or out_proj (K = 2048), EPI_RESIDUAL, plain (reference _torch.py:100-101,141,152), or
  * the hybrid's Mamba2 out_proj (K = 4096 = d_ssm, EPI_STORE: mamba_ssm out_proj of the prefill): a split-K GEMM
  * (one workgroup per 64-column block, K segment -- 8 x 1024 / 4 x 1024 / 4 x 512, the GEMV's wave split -- and

@@ -1,4 +1,5 @@
 """Shared test helpers: golden fixture loading and synthetic model construction."""
+import contextlib
 import json
 import math
 import os
@@ -10,6 +11,19 @@ from zonos_vibes_amd import synthetic as syn
 from zonos_vibes_amd.config import ZonosConfig
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+@contextlib.contextmanager
+def zmi_option(which, value):
+    """Set a zmi_set_option knob for the block and put back the value it had before (not the library's default)."""
+    from zonos_vibes_amd import _lib
+    lib = _lib.lib()
+    old = lib.zmi_get_option(which)
+    _lib.check(lib.zmi_set_option(which, value), "set_option")
+    try:
+        yield old
+    finally:
+        _lib.check(lib.zmi_set_option(which, old), "set_option")
 
 
 def load_golden(name):

@@ -32,19 +32,19 @@ def test_xcd_dealing_is_round_robin(model):
 
 @pytest.mark.parametrize("lc,n_new", [(160, 899), (40, 200)])
 def test_l2_handoffs_decode_the_same_codes_as_write_through(model, lc, n_new):
+    from tests.helpers import zmi_option
     from zonos_vibes_amd import _lib
     e = model.engine
     cond = _cond(7, model.config.backbone.d_model, lc)
     out = {}
     try:
         for mode in (1, 0):
-            _lib.check(e.lib.zmi_set_option(_lib.OPT_XC_HANDOFF, mode), "set_option")
-            e._build_plan()  # graphs hold the launch arguments: capture again
-            out[mode] = model.generate(cond, max_new_tokens=n_new, sampling_params=dict(temperature=0.0),
-                                       progress_bar=False, chunk=128).cpu()
-            e.check_errors()
+            with zmi_option(_lib.OPT_XC_HANDOFF, mode):
+                e._build_plan()  # graphs hold the launch arguments: capture again
+                out[mode] = model.generate(cond, max_new_tokens=n_new, sampling_params=dict(temperature=0.0),
+                                           progress_bar=False, chunk=128).cpu()
+                e.check_errors()
     finally:
-        _lib.check(e.lib.zmi_set_option(_lib.OPT_XC_HANDOFF, 0), "set_option")
-        e._build_plan()
+        e._build_plan()  # with the option back at the value it had before
     assert out[0].shape[-1] == n_new
     assert torch.equal(out[0], out[1])

@@ -51,6 +51,15 @@ class GemvArgs(ctypes.Structure):
     ]
 
 
+FORM_BODY, FORM_ROWS, FORM_ROWS_DENSE = 0, 1, 2  # GemvForm.kind
+
+
+class GemvForm(ctypes.Structure):
+    """ZmiGemvForm: the launch form zmi_gemv_form reports (pro: 0 plain, 1 LayerNorm, else PRO_*)."""
+    _fields_ = [("kind", c_int), ("G", c_int), ("W", c_int), ("NL", c_int), ("RT", c_int), ("ntw", c_int),
+                ("pro", c_int), ("n_cb", c_int), ("n_rt", c_int), ("rpw", c_int)]
+
+
 class Prefetch(ctypes.Structure):
     _fields_ = [("ptr", c_void_p * 2), ("bytes", c_int64 * 2), ("sink", c_void_p), ("blocks", c_int),
                 ("reserved", c_int)]
@@ -112,6 +121,7 @@ COND_EMBED, COND_VECTOR, COND_FOURIER, COND_LINEAR, COND_PASSTHROUGH = range(5)
 _SIGS = {
     "zmi_pack_weight": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "zmi_gemv_launch": (c_int, [ctypes.POINTER(GemvArgs), c_int, c_void_p]),
+    "zmi_gemv_form": (c_int, [ctypes.POINTER(GemvArgs), c_int, ctypes.POINTER(GemvForm)]),
     "zmi_layernorm_rows": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_int,
                                    c_void_p]),
     "zmi_attention": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,

@@ -43,8 +43,8 @@ __global__ void pack_kernel(const bf16_t* __restrict__ src, uint4* __restrict__ 
 
 }  // namespace
 
-extern "C" int zmi_gemv_launch(const ZmiGemvArgs* args, int epi, void* stream) {
-  const ZmiGemvArgs& a = *args;
+// the argument checks of zmi_gemv_launch (0 = accepted; else zmi_last_error is set)
+static int check_args(const ZmiGemvArgs& a, int epi) {
   zmi_gemv::Shape sh;
   if (a.N % 8) return zmi_fail_msg("gemv: N must be a multiple of 8");
   if (!zmi_gemv::shape_for(a.K, &sh))
@@ -67,6 +67,26 @@ extern "C" int zmi_gemv_launch(const ZmiGemvArgs* args, int epi, void* stream) {
        (epi != ZMI_EPI_SWIGLU && epi != ZMI_EPI_RESIDUAL && epi != ZMI_EPI_F32)))
     return zmi_fail_msg("gemv: fp8 weights need w_exp (8-byte aligned) and are built for the plain / LayerNorm prologue, "
                         "K = 512, 1024, 2048 or 8192 and the SWIGLU, RESIDUAL and F32 epilogues");
+  if (epi < ZMI_EPI_STORE || epi > ZMI_EPI_F32) return zmi_fail_msg("gemv: unknown epilogue");
+  return 0;
+}
+
+static int not_built(const ZmiGemvArgs& a) {
+  if (a.pro != ZMI_PRO_AUTO)
+    return zmi_fail_msg("gemv: prologue not built for this K / epilogue / row count (ADDLN: K 512 or 2048; GRMS: K "
+                        "1024 or 4096, ZMI_EPI_STORE, rows within the LDS image)");
+  return zmi_fail_msg("gemv: form not built for these arguments (groups, rows within the LDS image)");
+}
+
+extern "C" int zmi_gemv_form(const ZmiGemvArgs* args, int epi, ZmiGemvForm* out) {
+  if (const int rc = check_args(*args, epi)) return rc;
+  if (!zmi_gemv::form_for(*args, epi, out)) return not_built(*args);
+  return 0;
+}
+
+extern "C" int zmi_gemv_launch(const ZmiGemvArgs* args, int epi, void* stream) {
+  const ZmiGemvArgs& a = *args;
+  if (const int rc = check_args(a, epi)) return rc;
   hipStream_t s = (hipStream_t)stream;
   hipError_t e;
   switch (epi) {
@@ -78,9 +98,7 @@ extern "C" int zmi_gemv_launch(const ZmiGemvArgs* args, int epi, void* stream) {
     case ZMI_EPI_F32: e = zmi_gemv::launch_epi5(a, s); break;
     default: return zmi_fail_msg("gemv: unknown epilogue");
   }
-  if (e == hipErrorInvalidValue && a.pro != ZMI_PRO_AUTO)
-    return zmi_fail_msg("gemv: prologue not built for this K / epilogue / row count (ADDLN: K 512 or 2048; GRMS: K "
-                        "1024 or 4096, ZMI_EPI_STORE, rows within the LDS image)");
+  if (e == hipErrorInvalidValue && a.pro != ZMI_PRO_AUTO) return not_built(a);
   ZMI_CHECK(e);
   return 0;
 }

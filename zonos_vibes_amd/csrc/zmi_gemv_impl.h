@@ -987,16 +987,77 @@ inline int groups_for(const ZmiGemvArgs& a, const Shape& s) {
   return (a.K == 2048 && a.N / 8 >= 384 && (a.ln_w != nullptr || a.pro != ZMI_PRO_AUTO || a.M > 4)) ? 2 : 1;
 }
 
+// where the many-row form beats gemv_body's 4-group tile loop (C3 decode shapes, tools/kernel_bench.py
+// --gemm-rows 1,0): 128 rows qkv 18.1 -> 13.0 us, fc1 41.9 -> 31.1, heads 36.9 -> 24.0, out_proj 9.8 -> 7.0;
+// 64 rows qkv 12.1 -> 9.6, fc1 26.2 -> 22.8, heads 21.3 -> 15.3 but out_proj 5.8 -> 6.8; 32 rows only the
+// wide ones (heads 13.3 -> 11.6; qkv 7.6 -> 9.7, out_proj 5.8 -> 8.3)
+inline bool rows_form(int M, int N) { return M > 64 || (M > 32 && N >= 3072) || N >= 8192; }
+// the launches that take the many-row form: plain bf16 K = 2048 rows past one tile, no forced group count
+inline bool rows_launch(const ZmiGemvArgs& a) {
+  return a.w_fmt == ZMI_WFMT_BF16 && a.K == 2048 && a.M > GR_RT && a.ln_w == nullptr && a.pro == ZMI_PRO_AUTO &&
+         a.groups == 0 && zmi_option(ZMI_OPT_GEMM_ROWS) && rows_form(a.M, a.N);
+}
+
+// gemv_body's (G, W, NL, RT) instantiations that are built with every prologue / tile form of launch_g; the 4-group
+// (4, 4, 8, 16) one is built as the plain tile loop only (groups_for's many-row plain case)
+#define ZMI_GEMV_SHAPES(X) X(1, 2, 4, 16) X(1, 4, 4, 16) X(1, 4, 8, 16) X(2, 4, 8, 16) X(1, 4, 16, 16) X(1, 8, 16, 8) X(2, 8, 16, 8)
+
+// the prologue of a shape, where it is built: fp8 weights for LayerNorm'd or plain rows and not for K = 4096 (no fp8
+// projection has it); ADDLN (the hybrid blocks' d_model GEMVs) for K 512 / 2048; GRMS (the Mamba2 out_proj, K = d_ssm)
+// for K 1024 / 4096 with the store epilogue, GRMS_G (the same from g = y * gate rows) on one tile (decode)
+constexpr bool pro_built(int K, int epi, int pro, bool f8) {
+  if (pro == PRO_ADDLN) return !f8 && (K == 512 || K == 2048) && epi != ZMI_EPI_RESIDUAL && epi != ZMI_EPI_F32;
+  if (pro == PRO_GRMS || pro == PRO_GRMSG) return !f8 && (K == 1024 || K == 4096) && epi == ZMI_EPI_STORE;
+  return !f8 || K != 4096;
+}
+
+inline size_t img_bytes(int K, int rows, int nwv, int rt, int pro) {
+  switch (K) {
+    case 512: return Img<512>::bytes(rows, nwv, rt, pro);
+    case 1024: return Img<1024>::bytes(rows, nwv, rt, pro);
+    case 2048: return Img<2048>::bytes(rows, nwv, rt, pro);
+    case 4096: return Img<4096>::bytes(rows, nwv, rt, pro);
+    default: return Img<8192>::bytes(rows, nwv, rt, pro);
+  }
+}
+
+// The form a launch takes: the kernel (gemv_body / the many-row form, M8 or dense pairs), its (G, W, NL, RT)
+// instantiation, single-tile or tile loop, the resolved prologue and the grid's geometry. Every launch<EPI>() dispatches
+// on what this returns and zmi_gemv_form reports it; false = not built (zmi_gemv_launch refuses).
+inline bool form_for(const ZmiGemvArgs& a, int epi, ZmiGemvForm* f) {
+  Shape sh;
+  if (!shape_for(a.K, &sh)) return false;
+  const bool f8 = a.w_fmt == ZMI_WFMT_FP8;
+  // fp8 weights run gemv_body's tile loop for every M: the many-row form (and the split-K GEMM) read bf16 weights
+  // only. All forms agree bit for bit, so this costs many-row speed, never bits.
+  if (f8 && epi != ZMI_EPI_SWIGLU && epi != ZMI_EPI_RESIDUAL && epi != ZMI_EPI_F32) return false;
+  if (rows_launch(a)) {
+    const int n_cb = (a.N / 8 + GR_G - 1) / GR_G, n_rt = (a.M + GR_RT - 1) / GR_RT;
+    *f = {(zmi_option(ZMI_OPT_GEMM_ROWS) & 2) ? ZMI_FORM_ROWS_DENSE : ZMI_FORM_ROWS, GR_G, 4, 8, GR_RT, 0, PRO_PLAIN,
+          n_cb, n_rt, rows_per_wg(n_cb, n_rt, zmi_cu_count())};  // one workgroup per CU
+    return true;
+  }
+  const int g = groups_for(a, sh);
+  const int pro = a.pro != ZMI_PRO_AUTO ? a.pro : (a.ln_w != nullptr ? PRO_LN : PRO_PLAIN);  // ZMI_PRO_* = PRO_*
+  const int ntw = a.M <= sh.RT;  // one row tile: each weight is read once, the non-temporal single-tile instantiation
+  bool built = g == 4 && sh.W == 4 && sh.NL == 8 && sh.RT == 16 && !ntw && pro == PRO_PLAIN;
+#define ZMI_SHAPE(G_, W_, NL_, RT_) built = built || (g == G_ && sh.W == W_ && sh.NL == NL_ && sh.RT == RT_);
+  ZMI_GEMV_SHAPES(ZMI_SHAPE)
+#undef ZMI_SHAPE
+  if (!built) return false;  // e.g. groups = 2 outside the K = 2048 / 8192 shapes
+  if (!pro_built(a.K, epi, pro, f8) || (pro == PRO_GRMSG && !ntw)) return false;
+  if (img_bytes(a.K, a.M < sh.RT ? a.M : sh.RT, g * sh.W, sh.RT, pro) > LDS_MAX) return false;
+  const int n_cb = (a.N / 8 + g - 1) / g, n_rt = (a.M + sh.RT - 1) / sh.RT;
+  *f = {ZMI_FORM_BODY, g, sh.W, sh.NL, sh.RT, ntw, pro, n_cb, n_rt, rows_per_wg(n_cb, n_rt, a.K == 8192 ? 256 : 512)};
+  return true;
+}
+
 template <int G, int W, int NL, int RT, int PRO, int EPI, int NTW, int FMT = ZMI_WFMT_BF16>
-hipError_t launch_p(const ZmiGemvArgs& a, hipStream_t s) {
+hipError_t launch_p(const ZmiGemvArgs& a, hipStream_t s, const ZmiGemvForm& f) {
   constexpr int K = W * NL * 64;
   auto fn = gemv_fn<FMT, G, W, NL, RT, PRO, EPI, NTW>();
-  const int n_cb = (a.N / 8 + G - 1) / G;
-  const int n_rt = (a.M + RT - 1) / RT;
   size_t lds = Img<K>::bytes(a.M < RT ? a.M : RT, G * W, RT, PRO);
-  if (lds > LDS_MAX) return hipErrorInvalidValue;
-  const int rpw = rows_per_wg(n_cb, n_rt, K == 8192 ? 256 : 512);
-  const int64_t blocks = block_count(n_cb, n_rt, rpw);
+  const int64_t blocks = block_count(f.n_cb, f.n_rt, f.rpw);
   if (NTW && zmi_option(ZMI_OPT_GEMV_SPREAD)) {
     // a decode launch streams each weight once: its rate is the number of CUs it keeps busy (one CU
     // pulls ~25 GB/s), so reserve LDS such that at most ceil(blocks / CUs) workgroups share a CU
@@ -1013,91 +1074,70 @@ hipError_t launch_p(const ZmiGemvArgs& a, hipStream_t s) {
     if (attr != hipSuccess) return attr;
   }
   if (blocks > 0x7fffffff) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(G * W * 64), lds, s, a, n_cb, n_rt, rpw);
+  hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(G * W * 64), lds, s, a, f.n_cb, f.n_rt, f.rpw);
   return hipGetLastError();
 }
 
-// one row tile (M <= RT: each weight is read once, the non-temporal single-tile instantiation) or the row-tile loop
+// one row tile (M <= RT: the single-tile instantiation) or the row-tile loop
 template <int G, int W, int NL, int RT, int PRO, int EPI, int FMT = ZMI_WFMT_BF16>
-hipError_t launch_tiles(const ZmiGemvArgs& a, hipStream_t s) {
-  return a.M <= RT ? launch_p<G, W, NL, RT, PRO, EPI, 1, FMT>(a, s) : launch_p<G, W, NL, RT, PRO, EPI, 0, FMT>(a, s);
+hipError_t launch_tiles(const ZmiGemvArgs& a, hipStream_t s, const ZmiGemvForm& f) {
+  return f.ntw ? launch_p<G, W, NL, RT, PRO, EPI, 1, FMT>(a, s, f) : launch_p<G, W, NL, RT, PRO, EPI, 0, FMT>(a, s, f);
 }
 
-// the prologue of a shape, where it is built: fp8 weights for LayerNorm'd or plain rows and not for K = 4096 (no fp8
-// projection has it); ADDLN (the hybrid blocks' d_model GEMVs) for K 512 / 2048; GRMS (the Mamba2 out_proj, K = d_ssm)
-// for K 1024 / 4096 with the store epilogue, GRMS_G (the same from g = y * gate rows) on one tile (decode)
+// the prologues of a shape: only those pro_built names are instantiated
 template <int G, int W, int NL, int RT, int EPI, int FMT>
-hipError_t launch_g(const ZmiGemvArgs& a, hipStream_t s) {
+hipError_t launch_g(const ZmiGemvArgs& a, hipStream_t s, const ZmiGemvForm& f) {
   constexpr int K = W * NL * 64;
   constexpr bool F8 = FMT == ZMI_WFMT_FP8;
-  if constexpr (!F8 && (K == 512 || K == 2048) && EPI != ZMI_EPI_RESIDUAL && EPI != ZMI_EPI_F32)
-    if (a.pro == ZMI_PRO_ADDLN) return launch_tiles<G, W, NL, RT, PRO_ADDLN, EPI>(a, s);
-  if constexpr (!F8 && (K == 1024 || K == 4096) && EPI == ZMI_EPI_STORE) {
-    if (a.pro == ZMI_PRO_GRMS) return launch_tiles<G, W, NL, RT, PRO_GRMS, EPI>(a, s);
-    if (a.pro == ZMI_PRO_GRMS_G && a.M <= RT) return launch_p<G, W, NL, RT, PRO_GRMSG, EPI, 1>(a, s);
+  if constexpr (pro_built(K, EPI, PRO_ADDLN, F8))
+    if (f.pro == PRO_ADDLN) return launch_tiles<G, W, NL, RT, PRO_ADDLN, EPI>(a, s, f);
+  if constexpr (pro_built(K, EPI, PRO_GRMS, F8)) {
+    if (f.pro == PRO_GRMS) return launch_tiles<G, W, NL, RT, PRO_GRMS, EPI>(a, s, f);
+    if (f.pro == PRO_GRMSG && f.ntw) return launch_p<G, W, NL, RT, PRO_GRMSG, EPI, 1>(a, s, f);
   }
-  if constexpr (!F8 || K != 4096) {
-    if (a.pro == ZMI_PRO_AUTO && a.ln_w != nullptr) return launch_tiles<G, W, NL, RT, PRO_LN, EPI, FMT>(a, s);
-    if (a.pro == ZMI_PRO_AUTO) return launch_tiles<G, W, NL, RT, PRO_PLAIN, EPI, FMT>(a, s);
+  if constexpr (pro_built(K, EPI, PRO_LN, F8)) {
+    if (f.pro == PRO_LN) return launch_tiles<G, W, NL, RT, PRO_LN, EPI, FMT>(a, s, f);
+    if (f.pro == PRO_PLAIN) return launch_tiles<G, W, NL, RT, PRO_PLAIN, EPI, FMT>(a, s, f);
   }
   return hipErrorInvalidValue;
 }
 
-// where the many-row form beats gemv_body's 4-group tile loop (C3 decode shapes, tools/kernel_bench.py
-// --gemm-rows 1,0): 128 rows qkv 18.1 -> 13.0 us, fc1 41.9 -> 31.1, heads 36.9 -> 24.0, out_proj 9.8 -> 7.0;
-// 64 rows qkv 12.1 -> 9.6, fc1 26.2 -> 22.8, heads 21.3 -> 15.3 but out_proj 5.8 -> 6.8; 32 rows only the
-// wide ones (heads 13.3 -> 11.6; qkv 7.6 -> 9.7, out_proj 5.8 -> 8.3)
-inline bool rows_form(int M, int N) { return M > 64 || (M > 32 && N >= 3072) || N >= 8192; }
-
 template <int EPI, int GPW, bool DN>
-hipError_t launch_rows(const ZmiGemvArgs& a, hipStream_t s) {
+hipError_t launch_rows(const ZmiGemvArgs& a, hipStream_t s, const ZmiGemvForm& f) {
   auto fn = gemm_rows_kernel<EPI, GPW, DN>;
-  const int n_cb = (a.N / 8 + GR_G - 1) / GR_G;
-  const int n_rt = (a.M + GR_RT - 1) / GR_RT;
-  const int rpw = rows_per_wg(n_cb, n_rt, zmi_cu_count());  // one workgroup per CU
-  const int64_t blocks = block_count(n_cb, n_rt, rpw);
+  const int64_t blocks = block_count(f.n_cb, f.n_rt, f.rpw);
   static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(fn),
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX);
   if (attr != hipSuccess) return attr;
   if (blocks > 0x7fffffff) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(GR_G * 4 / GPW * 64 / (DN ? 2 : 1)), GR_LDS, s, a, n_cb, n_rt, rpw);
+  hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(GR_G * 4 / GPW * 64 / (DN ? 2 : 1)), GR_LDS, s, a, f.n_cb, f.n_rt,
+                     f.rpw);
   return hipGetLastError();
 }
 
-// gemv_body's launches of one weight format: the (G, W, NL, RT) instantiations that are built
+// gemv_body's launches of one weight format
 template <int EPI, int FMT>
-hipError_t launch_shape(const ZmiGemvArgs& a, hipStream_t s, const Shape& sh, int g) {
-  if (g == 4 && sh.W == 4 && sh.NL == 8 && sh.RT == 16 && a.M > sh.RT && a.ln_w == nullptr && a.pro == ZMI_PRO_AUTO)
-    return launch_p<4, 4, 8, 16, PRO_PLAIN, EPI, 0, FMT>(a, s);  // groups_for's many-row plain case only
+hipError_t launch_shape(const ZmiGemvArgs& a, hipStream_t s, const ZmiGemvForm& f) {
+  if (f.G == 4) return launch_p<4, 4, 8, 16, PRO_PLAIN, EPI, 0, FMT>(a, s, f);
 #define ZMI_SHAPE(G_, W_, NL_, RT_) \
-  if (g == G_ && sh.W == W_ && sh.NL == NL_ && sh.RT == RT_) return launch_g<G_, W_, NL_, RT_, EPI, FMT>(a, s);
-  ZMI_SHAPE(1, 2, 4, 16)
-  ZMI_SHAPE(1, 4, 4, 16)
-  ZMI_SHAPE(1, 4, 8, 16)
-  ZMI_SHAPE(2, 4, 8, 16)
-  ZMI_SHAPE(1, 4, 16, 16)
-  ZMI_SHAPE(1, 8, 16, 8)
-  ZMI_SHAPE(2, 8, 16, 8)
+  if (f.G == G_ && f.W == W_ && f.NL == NL_ && f.RT == RT_) return launch_g<G_, W_, NL_, RT_, EPI, FMT>(a, s, f);
+  ZMI_GEMV_SHAPES(ZMI_SHAPE)
 #undef ZMI_SHAPE
-  return hipErrorInvalidValue;  // e.g. groups = 2 outside the LayerNorm'd K = 2048 shape
+  return hipErrorInvalidValue;
 }
 
 template <int EPI>
 hipError_t launch(const ZmiGemvArgs& a, hipStream_t s) {
-  Shape sh;
-  if (!shape_for(a.K, &sh)) return hipErrorInvalidValue;
-  const int g = groups_for(a, sh);
+  ZmiGemvForm f;
+  if (!form_for(a, EPI, &f)) return hipErrorInvalidValue;
+  if (f.kind == ZMI_FORM_ROWS_DENSE) return launch_rows<EPI, 1, true>(a, s, f);
+  if (f.kind == ZMI_FORM_ROWS) return launch_rows<EPI, 2, false>(a, s, f);
   if (a.w_fmt == ZMI_WFMT_FP8) {
-    // fp8 weights run gemv_body's tile loop for every M: the many-row form below (and the split-K GEMM) read bf16
-    // weights only. All forms agree bit for bit, so this costs many-row speed, never bits.
     if constexpr (EPI == ZMI_EPI_SWIGLU || EPI == ZMI_EPI_RESIDUAL || EPI == ZMI_EPI_F32)
-      return launch_shape<EPI, ZMI_WFMT_FP8>(a, s, sh, g);
+      return launch_shape<EPI, ZMI_WFMT_FP8>(a, s, f);
     return hipErrorInvalidValue;
   }
-  if (a.K == 2048 && a.M > GR_RT && a.ln_w == nullptr && a.pro == ZMI_PRO_AUTO && a.groups == 0 &&
-      zmi_option(ZMI_OPT_GEMM_ROWS) && rows_form(a.M, a.N))
-    return (zmi_option(ZMI_OPT_GEMM_ROWS) & 2) ? launch_rows<EPI, 1, true>(a, s) : launch_rows<EPI, 2, false>(a, s);
-  return launch_shape<EPI, ZMI_WFMT_BF16>(a, s, sh, g);
+  return launch_shape<EPI, ZMI_WFMT_BF16>(a, s, f);
 }
 
 }  // namespace zmi_gemv
