@@ -531,6 +531,18 @@ int zmi_mamba2_scan(const ZmiMamba2Args* args, int seq_len, void* stream);
  * oracle). ws: >= zmi_mamba2_scan_ws_bytes(M, d_ssm, nheads). */
 int zmi_mamba2_scan_ws(const ZmiMamba2Args* args, int seq_len, void* ws, int64_t ws_bytes, void* stream);
 int64_t zmi_mamba2_scan_ws_bytes(int m, int d_ssm, int nheads);
+/* zmi_mamba2_scan_ws over ragged sequences, one pass for all of them. Sequence i of the ZmiAttnSeq table owns rows
+ * q_row0 .. q_row0 + len - 1 of zxbcdt and y, starts from an empty state (pos0 must be 0) and leaves its final SSM
+ * state and conv ring in state row kv_row (args->row_kv is not read). args->M is the row count of the buffers: it
+ * bounds the table and sizes ws (>= zmi_mamba2_scan_ws_bytes(M, d_ssm, nheads)). The form is chosen per sequence,
+ * as zmi_mamba2_scan_ws would for it alone (ZMI_OPT_SCAN_PQ 0: up to 256 positions the SSD form, longer ones the
+ * recurrence on 4 workgroups; a mixed table is two scan launches), the longest sequences dispatched first, and each
+ * sequence's y, state and ring are bit for bit those of zmi_mamba2_scan_ws on it alone. Only the listed rows of y and
+ * the listed state rows are written; sequences of len 0 are skipped. seqs is the device table, seqs_host its host
+ * copy, checked before anything is launched: a negative n_seq, len, q_row0 or kv_row, rows past M, pos0 != 0, two
+ * live sequences sharing rows or a kv_row, or a small ws are refused (non-zero, zmi_last_error, nothing written). */
+int zmi_mamba2_scan_seqs(const ZmiMamba2Args* args, const ZmiAttnSeq* seqs, int n_seq, const ZmiAttnSeq* seqs_host,
+                         void* ws, int64_t ws_bytes, void* stream);
 /* layer_norm_fn(hidden, w, b, residual, prenorm=True): s = hidden + residual (fp32; hidden may be NULL:
  * s = residual), residual <- bf16(s) if store_residual, out = LayerNorm(s) bf16; k in {512 .. 4096}. */
 int zmi_add_layernorm(const void* hidden, int ldh, void* residual, int ldr, int m, int k, const void* w,

@@ -20,6 +20,9 @@
 //              reads), so the workgroups of one row never race; negative positions read as zero.
 //   ssm state  bf16 [row][nheads][headdim 64][d_state 128] (the reference keeps it in the cache dtype).
 #include <algorithm>
+#include <climits>
+#include <utility>
+#include <vector>
 
 #include "zmi_common.h"
 #include "zmi_kernels.h"
@@ -126,7 +129,8 @@ __global__ __launch_bounds__(MB_NT) void mamba2_scan_kernel(const ZmiMamba2Args 
 }
 
 // ---------------------------------------------------------------------------- parallel prefill scan
-// zmi_mamba2_scan_ws: the same Mamba2.forward from an empty state in two launches.
+// zmi_mamba2_scan_ws (sequences of one length) and zmi_mamba2_scan_seqs (ragged sequences from a ZmiAttnSeq table, a
+// form per sequence: up to three launches): the same Mamba2.forward from an empty state in two launches.
 //  (1) mamba2_conv_kernel, one workgroup per row: causal conv + SiLU of every xBC channel (conv4, bf16-rounded as
 //      the reference's conv output tensor) into the workspace, dt = softplus(dt + dt_bias) and dA = exp(A dt) per
 //      head, and, on each sequence's last row, the conv ring's four slots (the last raw inputs, zero below 0).
@@ -140,10 +144,72 @@ __global__ __launch_bounds__(MB_NT) void mamba2_scan_kernel(const ZmiMamba2Args 
 constexpr int S2_NB = MB_DS / 8;        // 16 n-blocks of 8 state columns
 constexpr int S2_TT = 32;               // positions staged per tile
 
-__global__ __launch_bounds__(256) void mamba2_conv_kernel(const ZmiMamba2Args a, int seq_len, bf16_t* xc, float* dts,
-                                                          float* das) {
+// Which rows form which sequence, for the three prefill kernels. Uniform (seqs null, zmi_mamba2_scan_ws): sequence k
+// is rows k seq_len .. + seq_len - 1, its state row row_kv[first row] (or k). Ragged (zmi_mamba2_scan_seqs): the
+// ZmiAttnSeq table; a scan launch covers the sequences of its form, lo < len <= hi, longest first (ties in table
+// order), so the long ones start while the chip is empty. The host has checked the table (rows inside M, no overlap).
+struct ScanSeqs {
+  const ZmiAttnSeq* seqs;
+  int n_seq, seq_len, lo, hi;
+};
+struct ScanSeq {
+  int row0, T, idx;  // T == 0: no sequence
+};
+
+__device__ __forceinline__ bool scan_rows_ok(const ZmiAttnSeq& s, int m) {
+  return s.len > 0 && s.q_row0 >= 0 && s.q_row0 <= m - s.len;
+}
+
+// the k-th sequence of a scan launch; sh: one LDS word (ragged: every thread of the workgroup must call)
+__device__ __forceinline__ ScanSeq scan_seq_at(const ZmiMamba2Args& a, const ScanSeqs& q, int k, int* sh) {
+  if (!q.seqs) return ScanSeq{k * q.seq_len, q.seq_len, k};
+  if (threadIdx.x == 0) *sh = -1;
+  __syncthreads();
+  for (int i = threadIdx.x; i < q.n_seq; i += blockDim.x) {
+    const int len = q.seqs[i].len;
+    if (len <= q.lo || len > q.hi) continue;
+    int rank = 0;  // sequences of this form ahead of i
+    for (int j = 0; j < q.n_seq; ++j) {
+      const int lj = q.seqs[j].len;
+      rank += (lj > q.lo && lj <= q.hi && (lj > len || (lj == len && j < i))) ? 1 : 0;
+    }
+    if (rank == k) *sh = i;
+  }
+  __syncthreads();
+  const int i = *sh;
+  if (i < 0 || !scan_rows_ok(q.seqs[i], a.M)) return ScanSeq{0, 0, -1};
+  return ScanSeq{q.seqs[i].q_row0, q.seqs[i].len, i};
+}
+
+// the sequence that holds `row` (ragged: every thread of the workgroup must call; none: T == 0)
+__device__ __forceinline__ ScanSeq scan_seq_of_row(const ZmiMamba2Args& a, const ScanSeqs& q, int row, int* sh) {
+  if (!q.seqs) return ScanSeq{row / q.seq_len * q.seq_len, q.seq_len, row / q.seq_len};
+  if (threadIdx.x == 0) *sh = -1;
+  __syncthreads();
+  for (int i = threadIdx.x; i < q.n_seq; i += blockDim.x) {
+    const ZmiAttnSeq s = q.seqs[i];
+    if (scan_rows_ok(s, a.M) && row >= s.q_row0 && row - s.q_row0 < s.len) *sh = i;
+  }
+  __syncthreads();
+  const int i = *sh;
+  if (i < 0) return ScanSeq{0, 0, -1};
+  return ScanSeq{q.seqs[i].q_row0, q.seqs[i].len, i};
+}
+
+// the state row (conv ring, SSM state) a sequence leaves its final state in
+__device__ __forceinline__ int scan_kv(const ZmiMamba2Args& a, const ScanSeqs& q, const ScanSeq& s) {
+  if (q.seqs) return q.seqs[s.idx].kv_row;
+  return a.row_kv ? a.row_kv[s.row0] : s.idx;
+}
+
+__global__ __launch_bounds__(256) void mamba2_conv_kernel(const ZmiMamba2Args a, const ScanSeqs sqs, bf16_t* xc,
+                                                          float* dts, float* das) {
   // one thread per (row, channel): grid (rows, channel blocks of 256), every load of the launch in flight at once
-  const int row = blockIdx.x, sq = row / seq_len, q = row - sq * seq_len, row0 = sq * seq_len;
+  __shared__ int seq_sh;
+  const int row = blockIdx.x;
+  const ScanSeq sq = scan_seq_of_row(a, sqs, row, &seq_sh);
+  if (sq.T == 0) return;  // a row of no sequence: nothing read, nothing written
+  const int seq_len = sq.T, row0 = sq.row0, q = row - row0;
   const int conv_dim = a.d_ssm + 2 * MB_DS, c = blockIdx.y * 256 + threadIdx.x;
   const bf16_t* zx0 = reinterpret_cast<const bf16_t*>(a.zxbcdt) + (size_t)row0 * a.ld_zx + a.d_ssm;
   if (c < conv_dim) {
@@ -157,7 +223,7 @@ __global__ __launch_bounds__(256) void mamba2_conv_kernel(const ZmiMamba2Args a,
     }
     xc[(size_t)row * conv_dim + c] = (bf16_t)f2bf(conv4(cw + (size_t)c * MB_DC, bf2f(cb[c]), r[0], r[1], r[2], r[3]));
     if (q == seq_len - 1) {  // the conv ring: slot qq % 4 holds the raw input of qq, for the last d_conv positions
-      const int kv = a.row_kv ? a.row_kv[row0] : sq;
+      const int kv = scan_kv(a, sqs, sq);
       bf16_t* ring = reinterpret_cast<bf16_t*>(a.conv_ring) + (size_t)kv * MB_DC * conv_dim;
 #pragma unroll
       for (int k = 0; k < MB_DC; ++k) {
@@ -194,12 +260,15 @@ extern "C" int zmi_scan_stamps_read(void* dst, size_t bytes) {
 #endif
 
 template <int PQ>
-__global__ __launch_bounds__(256) void mamba2_scan2_kernel(const ZmiMamba2Args a, int seq_len, const bf16_t* xc,
+__global__ __launch_bounds__(256) void mamba2_scan2_kernel(const ZmiMamba2Args a, const ScanSeqs sqs, const bf16_t* xc,
                                                            const float* dts, const float* das) {
   constexpr int PW = MB_HD / PQ, PR = PW / 16;  // head dims per workgroup, rows per thread
-  const int pq = blockIdx.x % PQ, sh = blockIdx.x / PQ, h = sh % a.nheads, sq = sh / a.nheads;
-  const int row0 = sq * seq_len, conv_dim = a.d_ssm + 2 * MB_DS;
-  const int kv = a.row_kv ? a.row_kv[row0] : sq;
+  __shared__ int seq_sh;
+  const int pq = blockIdx.x % PQ, sh = blockIdx.x / PQ, h = sh % a.nheads;
+  const ScanSeq sq = scan_seq_at(a, sqs, sh / a.nheads, &seq_sh);
+  if (sq.T == 0) return;
+  const int seq_len = sq.T, row0 = sq.row0, conv_dim = a.d_ssm + 2 * MB_DS;
+  const int kv = scan_kv(a, sqs, sq);
   const int t = threadIdx.x, pg = t / S2_NB, nb = t % S2_NB, p0 = pq * PW + pg * PR;
   __shared__ float xs[S2_TT][PW], bdt[S2_TT][MB_DS], cs[S2_TT][MB_DS], dA[S2_TT];
   const float Dh = a.D[h];
@@ -371,12 +440,15 @@ __device__ __forceinline__ uint32_t split_bf16(float v, uint32_t* lo) {
   return h;
 }
 
-__global__ __launch_bounds__(SSD_NT) void mamba2_ssd_kernel(const ZmiMamba2Args a, int seq_len, const bf16_t* xc,
+__global__ __launch_bounds__(SSD_NT) void mamba2_ssd_kernel(const ZmiMamba2Args a, const ScanSeqs sqs, const bf16_t* xc,
                                                          const float* dts) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int T = seq_len;
-  const int role = blockIdx.x & 1, sh = blockIdx.x >> 1, h = sh % a.nheads, sq = sh / a.nheads;
-  const int row0 = sq * T, conv_dim = a.d_ssm + 2 * MB_DS;
+  extern __shared__ __attribute__((aligned(16))) char smem[];  // sized for the launch's longest sequence
+  __shared__ int seq_sh;
+  const int role = blockIdx.x & 1, sh = blockIdx.x >> 1, h = sh % a.nheads;
+  const ScanSeq sq = scan_seq_at(a, sqs, sh / a.nheads, &seq_sh);
+  if (sq.T == 0 || sq.T > SSD_TMAX) return;
+  const int T = sq.T;  // this sequence's own length: its LDS layout and arithmetic are those of a launch of it alone
+  const int row0 = sq.row0, conv_dim = a.d_ssm + 2 * MB_DS;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const SsdLds L(T);
   float* cum = reinterpret_cast<float*>(smem);
@@ -528,7 +600,7 @@ __global__ __launch_bounds__(SSD_NT) void mamba2_ssd_kernel(const ZmiMamba2Args 
     // (3) state tiles (16 p x 16 n): wave w -> p tile w & 3, n tiles 4 (w >> 2) .. + 3; A = W^T and B fragments
     // gathered per k-block
     constexpr int NPW = MB_DS / 16 / (SSD_NT / 64 / 4);  // n tiles per wave
-    const int kv = a.row_kv ? a.row_kv[row0] : sq;
+    const int kv = scan_kv(a, sqs, sq);
     bf16_t* st = reinterpret_cast<bf16_t*>(a.ssm) + ((size_t)kv * a.nheads + h) * MB_HD * MB_DS;
     const int pi = wave & 3, nb = (wave >> 2) * NPW;
     f32x4_t acc[NPW];
@@ -720,47 +792,104 @@ extern "C" int64_t zmi_mamba2_scan_ws_bytes(int m, int d_ssm, int nheads) {
   return xc + 2 * (((int64_t)m * nheads * 4 + 255) / 256 * 256);
 }
 
-extern "C" int zmi_mamba2_scan_ws(const ZmiMamba2Args* a, int seq_len, void* ws, int64_t ws_bytes, void* stream) {
-  if (int e = check_mamba(a)) return e;
-  if (seq_len <= 0 || a->M % seq_len) return zmi_fail_msg("mamba2_scan_ws: M must be a multiple of seq_len > 0");
-  if (!ws || ws_bytes < zmi_mamba2_scan_ws_bytes(a->M, a->d_ssm, a->nheads))
-    return zmi_fail_msg("mamba2_scan_ws: workspace smaller than zmi_mamba2_scan_ws_bytes");
+namespace {
+
+// The conv + dt launch over the a->M rows, then the scan launches: n_ssd sequences in the SSD form (LDS for the
+// longest, t_max positions) and n_scan in mamba2_scan2_kernel<PQ>; `sq` says which rows are which sequence.
+int launch_scan(const ZmiMamba2Args* a, ScanSeqs sq, int n_ssd, int t_max, int n_scan, int pq, void* ws,
+                hipStream_t s) {
   const int64_t xcb = ((int64_t)a->M * (a->d_ssm + 2 * MB_DS) * 2 + 255) / 256 * 256;
   const int64_t hb = ((int64_t)a->M * a->nheads * 4 + 255) / 256 * 256;
   bf16_t* xc = (bf16_t*)ws;
   float* dts = (float*)((char*)ws + xcb);
   float* das = (float*)((char*)ws + xcb + hb);
-  hipStream_t s = (hipStream_t)stream;
   const int conv_dim = a->d_ssm + 2 * MB_DS;
+  sq.lo = 0, sq.hi = INT_MAX;
   hipLaunchKernelGGL(mamba2_conv_kernel, dim3((unsigned)a->M, (unsigned)((conv_dim + 255) / 256)), dim3(256), 0, s, *a,
-                     seq_len, xc, dts, das);
+                     sq, xc, dts, das);
   ZMI_CHECK(hipGetLastError());
-  const int pq = zmi_option(ZMI_OPT_SCAN_PQ);
-  if (pq == 0 && seq_len <= SSD_TMAX) {  // the quadratic (SSD) form
-    const SsdLds L(seq_len);
+  if (n_ssd > 0) {  // the quadratic (SSD) form
+    const SsdLds L(t_max);
     const size_t lds = std::max(L.y_bytes(), L.s_bytes());
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&mamba2_ssd_kernel),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                       160 * 1024 - 16);  // the kernel's static LDS word comes off
     ZMI_CHECK(attr);
-    hipLaunchKernelGGL(mamba2_ssd_kernel, dim3((unsigned)(a->M / seq_len * a->nheads * 2)), dim3(SSD_NT), lds, s, *a,
-                       seq_len, (const bf16_t*)xc, (const float*)dts);
+    sq.lo = 0, sq.hi = SSD_TMAX;
+    hipLaunchKernelGGL(mamba2_ssd_kernel, dim3((unsigned)((int64_t)n_ssd * a->nheads * 2)), dim3(SSD_NT), lds, s, *a,
+                       sq, (const bf16_t*)xc, (const float*)dts);
     ZMI_CHECK(hipGetLastError());
-    return 0;
   }
-  const dim3 grid((unsigned)(a->M / seq_len * a->nheads * (pq == 0 ? 4 : pq)));
-  if (pq == 1)
-    hipLaunchKernelGGL(mamba2_scan2_kernel<1>, grid, dim3(256), 0, s, *a, seq_len, (const bf16_t*)xc,
-                       (const float*)dts, (const float*)das);
-  else if (pq == 2)
-    hipLaunchKernelGGL(mamba2_scan2_kernel<2>, grid, dim3(256), 0, s, *a, seq_len, (const bf16_t*)xc,
-                       (const float*)dts, (const float*)das);
-  else if (pq == 4 || pq == 0)  // 0: sequences past the quadratic form's reach
-    hipLaunchKernelGGL(mamba2_scan2_kernel<4>, grid, dim3(256), 0, s, *a, seq_len, (const bf16_t*)xc,
-                       (const float*)dts, (const float*)das);
-  else
-    return zmi_fail_msg("mamba2_scan_ws: ZMI_OPT_SCAN_PQ must be 1, 2 or 4");
-  ZMI_CHECK(hipGetLastError());
+  if (n_scan > 0) {
+    sq.lo = pq == 0 ? SSD_TMAX : 0, sq.hi = INT_MAX;  // 0: the sequences past the quadratic form's reach
+    const dim3 grid((unsigned)((int64_t)n_scan * a->nheads * (pq == 0 ? 4 : pq)));
+    if (pq == 1)
+      hipLaunchKernelGGL(mamba2_scan2_kernel<1>, grid, dim3(256), 0, s, *a, sq, (const bf16_t*)xc, (const float*)dts,
+                         (const float*)das);
+    else if (pq == 2)
+      hipLaunchKernelGGL(mamba2_scan2_kernel<2>, grid, dim3(256), 0, s, *a, sq, (const bf16_t*)xc, (const float*)dts,
+                         (const float*)das);
+    else
+      hipLaunchKernelGGL(mamba2_scan2_kernel<4>, grid, dim3(256), 0, s, *a, sq, (const bf16_t*)xc, (const float*)dts,
+                         (const float*)das);
+    ZMI_CHECK(hipGetLastError());
+  }
   return 0;
+}
+
+bool scan_pq_ok(int pq) { return pq == 0 || pq == 1 || pq == 2 || pq == 4; }
+
+}  // namespace
+
+extern "C" int zmi_mamba2_scan_ws(const ZmiMamba2Args* a, int seq_len, void* ws, int64_t ws_bytes, void* stream) {
+  if (int e = check_mamba(a)) return e;
+  if (seq_len <= 0 || a->M % seq_len) return zmi_fail_msg("mamba2_scan_ws: M must be a multiple of seq_len > 0");
+  if (!ws || ws_bytes < zmi_mamba2_scan_ws_bytes(a->M, a->d_ssm, a->nheads))
+    return zmi_fail_msg("mamba2_scan_ws: workspace smaller than zmi_mamba2_scan_ws_bytes");
+  const int pq = zmi_option(ZMI_OPT_SCAN_PQ);
+  if (!scan_pq_ok(pq)) return zmi_fail_msg("mamba2_scan_ws: ZMI_OPT_SCAN_PQ must be 0, 1, 2 or 4");
+  const bool ssd = pq == 0 && seq_len <= SSD_TMAX;
+  const int n = a->M / seq_len;
+  return launch_scan(a, ScanSeqs{nullptr, 0, seq_len, 0, 0}, ssd ? n : 0, seq_len, ssd ? 0 : n, pq, ws,
+                     (hipStream_t)stream);
+}
+
+extern "C" int zmi_mamba2_scan_seqs(const ZmiMamba2Args* a, const ZmiAttnSeq* seqs, int n_seq,
+                                    const ZmiAttnSeq* seqs_host, void* ws, int64_t ws_bytes, void* stream) {
+  if (int e = check_mamba(a)) return e;
+  if (n_seq < 0) return zmi_fail_msg("mamba2_scan_seqs: n_seq < 0");
+  if (n_seq > 0 && (!seqs || !seqs_host))
+    return zmi_fail_msg("mamba2_scan_seqs: the device table and its host copy are required");
+  const int pq = zmi_option(ZMI_OPT_SCAN_PQ);
+  if (!scan_pq_ok(pq)) return zmi_fail_msg("mamba2_scan_seqs: ZMI_OPT_SCAN_PQ must be 0, 1, 2 or 4");
+  std::vector<std::pair<int, int>> rows, kvs;  // (first row, row past the last), (state row, index) of the live ones
+  int n_ssd = 0, n_scan = 0, t_max = 0;
+  for (int i = 0; i < n_seq; ++i) {
+    const ZmiAttnSeq& s = seqs_host[i];
+    if (s.len < 0 || s.q_row0 < 0) return zmi_fail_msg("mamba2_scan_seqs: negative len or q_row0");
+    if (s.q_row0 > a->M - s.len) return zmi_fail_msg("mamba2_scan_seqs: a sequence's rows end past M");
+    if (s.pos0 != 0) return zmi_fail_msg("mamba2_scan_seqs: pos0 must be 0 (prefill from an empty state)");
+    if (s.kv_row < 0) return zmi_fail_msg("mamba2_scan_seqs: negative kv_row");
+    if (s.len == 0) continue;
+    rows.emplace_back(s.q_row0, s.q_row0 + s.len);
+    kvs.emplace_back(s.kv_row, i);
+    if (pq == 0 && s.len <= SSD_TMAX) {
+      ++n_ssd;
+      t_max = std::max(t_max, s.len);
+    } else {
+      ++n_scan;
+    }
+  }
+  std::sort(rows.begin(), rows.end());
+  std::sort(kvs.begin(), kvs.end());
+  for (size_t i = 1; i < rows.size(); ++i) {
+    if (rows[i].first < rows[i - 1].second) return zmi_fail_msg("mamba2_scan_seqs: two sequences share rows");
+    if (kvs[i].first == kvs[i - 1].first) return zmi_fail_msg("mamba2_scan_seqs: two sequences share a kv_row");
+  }
+  if (!ws || ws_bytes < zmi_mamba2_scan_ws_bytes(a->M, a->d_ssm, a->nheads))
+    return zmi_fail_msg("mamba2_scan_seqs: workspace smaller than zmi_mamba2_scan_ws_bytes");
+  if (rows.empty()) return 0;
+  return launch_scan(a, ScanSeqs{seqs, n_seq, 0, 0, 0}, n_ssd, t_max, n_scan, pq, ws, (hipStream_t)stream);
 }
 
 extern "C" int zmi_add_layernorm(const void* hidden, int ldh, void* residual, int ldr, int m, int k, const void* w,

@@ -102,7 +102,7 @@ def _round8(n: int) -> int:
 
 class HipEngine:
     hybrid = False
-    prefill_batch = True  # prefill_many packs several slots into one pass (the hybrid's scan does not)
+    prefill_batch = True  # prefill_many packs several slots into one pass (False on an instance: a loop of prefill())
 
     def __init__(self, cfg: ZonosConfig, device="cuda", max_slots: int = 1, max_seqlen: int = 2048,
                  max_prefill: int = 512, weights: str = "bf16"):

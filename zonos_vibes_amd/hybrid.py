@@ -10,7 +10,7 @@ hipGraph-captured decode loop, slots — is HipEngine's; this class only swaps t
   Mamba2 block   zmi_mamba_block: in_proj GEMV + the Mamba2 step (conv ring + SiLU + selective state
                  update) in one launch, granule hand-off (zmi_mamba2_step as its own launch above 16 rows)
                  -> out_proj GEMV with the GRMS prologue (RMSNormGated; prefill: zmi_gated_rmsnorm and
-                 zmi_mamba2_scan_ws over the sequence)
+                 zmi_mamba2_scan_seqs over the pass's ragged sequences)
   MHA block      QKV GEMV (non-interleaved rotary as interleaved pairs on permuted q / k rows, bf16
                  cos / sin as flash-attn caches them) -> attention kernel -> out_proj GEMV
   optional MLP   (add + LayerNorm) fc1 SwiGLU GEMV -> fc2 GEMV       (d_intermediate > 0)
@@ -24,6 +24,7 @@ from __future__ import annotations
 
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -49,7 +50,10 @@ def neox_pair_perm(hd: int) -> torch.Tensor:
 class HybridEngine(HipEngine):
     hybrid = True
 
-    prefill_batch = False  # the Mamba2 prefill scan takes one (cond, uncond) pair of sequences per pass
+    # prefill_many packs several slots into one pass: zmi_mamba2_scan_seqs takes the pass's ragged sequences in one
+    # scan, each bit for bit as alone. Measured on Zonos-v0.1-hybrid dims (tools/bench_hybrid_prefill.py, DESIGN.md
+    # 5p): the pass beats the loop of prefill() from 2 utterances on, so there is no threshold below which it loops.
+    prefill_batch = True
 
     def __init__(self, cfg, device="cuda", max_slots: int = 1, max_seqlen: int = 2048, max_prefill: int = 512):
         bb = cfg.backbone
@@ -103,7 +107,7 @@ class HybridEngine(HipEngine):
 
     def _alloc(self):
         super()._alloc()
-        md, R, P, dev = self.md, self.R, self.max_prefill, self.dev
+        md, R, P2, dev = self.md, self.R, self.pre_rows, self.dev  # P2: the rows of one prefill pass
         nm = self.L - len(self.attn_idx)
         z = lambda *shape, dt=torch.bfloat16: torch.zeros(*shape, dtype=dt, device=dev)  # noqa: E731
         with torch.cuda.stream(self.stream):
@@ -112,15 +116,15 @@ class HybridEngine(HipEngine):
             self.zero_rows = z(R, self.d)  # block 0's "hidden": s = 0 + residual, exactly the residual
             self.zx, self.yb, self.yn = z(R, md["d_in_proj"]), z(R, md["d_ssm"]), z(R, md["d_ssm"])
             self.gz = z(R, md["d_ssm"], dt=torch.float32)  # decode: g = y * gate (grms_g) or the gate z * sigmoid(z)
-            self.hid_pre, self.nrm_pre = z(2 * P, self.d), z(2 * P, self.d)
-            self.zx_pre, self.yb_pre, self.yn_pre = z(2 * P, md["d_in_proj"]), z(2 * P, md["d_ssm"]), z(2 * P, md["d_ssm"])
+            self.hid_pre, self.nrm_pre = z(P2, self.d), z(P2, self.d)
+            self.zx_pre, self.yb_pre, self.yn_pre = z(P2, md["d_in_proj"]), z(P2, md["d_ssm"]), z(P2, md["d_ssm"])
             self.hm = z(R, max(self.Fm, self.F, 1))
-            self.hm_pre = z(2 * P, max(self.Fm, self.F, 1))
+            self.hm_pre = z(P2, max(self.Fm, self.F, 1))
             self.conv_ring = z(nm, R, md["d_conv"], md["conv_dim"])
             self.ssm = z(nm, R, md["nheads"], md["headdim"], md["d_state"])
             self.mgran = z(nm, R, md["d_in_proj"] // 2, dt=torch.int64)  # zmi_mamba_block hand-off granules
-            ws = int(self.lib.zmi_mamba2_scan_ws_bytes(2 * P, md["d_ssm"], md["nheads"]))
-            self.scan_ws = z(ws, dt=torch.uint8)  # zmi_mamba2_scan_ws: conv output, dt, dA of the prefill rows
+            ws = int(self.lib.zmi_mamba2_scan_ws_bytes(P2, md["d_ssm"], md["nheads"]))
+            self.scan_ws = z(ws, dt=torch.uint8)  # zmi_mamba2_scan_seqs: conv output, dt, dA of the prefill rows
             self.rope = rope_table_neox(self.hd).to(dev)
         self.stream.synchronize()
 
@@ -235,9 +239,10 @@ class HybridEngine(HipEngine):
             _lib.check(lib.zmi_mamba2_step(ctypes.byref(a), s), "mamba2_step")
         return run
 
-    def _layer_items(self, lw, m, x, hid, nrm, zx, yb, yn, hm, q, attn, row_kv, row_pos, first, seq_len=None,
+    def _layer_items(self, lw, m, x, hid, nrm, zx, yb, yn, hm, q, attn, row_kv, row_pos, first, scan=None,
                      max_pos=None, table=None):
-        """Launches of one block over m rows (decode: seq_len None; prefill: sequences of seq_len rows)."""
+        """Launches of one block over m rows (decode: scan None; prefill: scan = the pass's sequence table as
+        (device pointer, host int32 [n_seq][4]), the rows' ragged sequences from position 0)."""
         d, md, qd = self.d, self.md, self.H * self.hd
         items = [("call", self._addln(None if first else hid, x, (lw["ln1_w"], lw["ln1_b"]), nrm, m))]
         if lw["kind"] == "attn":
@@ -245,7 +250,7 @@ class HybridEngine(HipEngine):
             qkv_n = (self.H + 2 * self.Hkv) * self.hd
             items.append(("gemv", self._gemv(lw["qkv"], nrm, m, qkv_n, d, _lib.EPI_QKV, q, qd,
                                              kv=(self.kc[j], self.vc[j]), row_kv=row_kv, row_pos=row_pos)))
-            if seq_len is None:
+            if scan is None:
                 items.append(("attn", j))
             else:
                 items.append(("call", lambda j=j: self._prefill_attention(j, q, m, row_kv, row_pos, max_pos, attn,
@@ -254,13 +259,14 @@ class HybridEngine(HipEngine):
         else:
             items.append(("gemv", self._gemv(lw["in_proj"], nrm, m, md["d_in_proj"], d, _lib.EPI_STORE, zx,
                                              md["d_in_proj"])))
-            if seq_len is None:
+            if scan is None:
                 items.append(("call", self._call_step(self._mamba_args(lw, zx, yb, m, row_pos, None))))
             else:
                 a = self._mamba_args(lw, zx, yb, m, row_pos, row_kv)
                 lib, s, wp, wn = self.lib, self.sptr, self.scan_ws.data_ptr(), self.scan_ws.numel()
-                items.append(("call", lambda a=a: _lib.check(lib.zmi_mamba2_scan_ws(ctypes.byref(a), seq_len, wp, wn,
-                                                                                    s), "mamba2_scan_ws")))
+                sp, sa = scan
+                items.append(("call", lambda a=a: _lib.check(lib.zmi_mamba2_scan_seqs(
+                    ctypes.byref(a), sp, len(sa), sa.ctypes.data, wp, wn, s), "mamba2_scan_seqs")))
             items.append(("call", self._gnorm(lw, yb, zx, yn, m)))
             items.append(("gemv", self._gemv(lw["out"], yn, m, d, md["d_ssm"], _lib.EPI_STORE, hid, d)))
         if lw.get("ff"):
@@ -360,28 +366,34 @@ class HybridEngine(HipEngine):
 
     # ------------------------------------------------------------------ prefill
     def _prefill_layers(self, m: int, max_pos: int, seqs):
-        """m rows = sequences of max_pos + 1 rows each, every sequence from position 0 (Mamba2.forward
-        from an empty cache; the reference's step() takes one token at a time after that). seqs: those sequences
-        as ZmiAttnSeq rows, for the MHA layers' tiled attention (HipEngine._prefill_table)."""
-        seq_len = max_pos + 1
-        if m % seq_len:
-            raise ValueError("hybrid prefill: rows must be whole sequences starting at position 0")
+        """The m rows of one pass through every layer. seqs: the rows' sequences as ZmiAttnSeq rows (q_row0, len,
+        kv_row, pos0), any lengths, every one from position 0 (Mamba2.forward from an empty cache; the reference's
+        step() takes one token at a time after that). One table, built and copied once per pass, serves the MHA
+        layers' tiled attention (HipEngine._prefill_table) and the Mamba2 layers' scan (zmi_mamba2_scan_seqs)."""
+        seqs = list(seqs)
+        sa = np.ascontiguousarray(np.asarray(seqs, dtype=np.int64).reshape(-1, 4), dtype=np.int32)
+        if (sa[:, 3] != 0).any():
+            raise ValueError("hybrid prefill: every sequence starts at position 0")
         table = self._prefill_table(seqs)
+        # the attention's device table begins with the sequence rows; prefill_attn = "rows" has none, so copy them
+        sdev = table[0] if table is not None else torch.from_numpy(sa.ravel()).to(self.dev)
+        scan = (sdev.data_ptr(), sa)
         for i, lw in enumerate(self.w["layers"]):
             for kind, item in self._layer_items(lw, m, self.x_pre, self.hid_pre, self.nrm_pre, self.zx_pre,
                                                 self.yb_pre, self.yn_pre, self.hm_pre, self.q_pre, self.attn_pre,
-                                                self.row_kv_pre, self.row_pos_pre, first=(i == 0), seq_len=seq_len,
+                                                self.row_kv_pre, self.row_pos_pre, first=(i == 0), scan=scan,
                                                 max_pos=max_pos, table=table):
                 if kind == "gemv":
                     self._run_gemv(item)
                 else:
                     item()
 
-    def _prefill_logits(self, s_len: int):
+    def _prefill_logits(self, s_len: int, off: int = 0):
+        """norm_f + heads of the last position of the cond / uncond sequences that start at row `off`."""
         d = self.d
-        off = (s_len - 1) * d * 2  # bytes: row s_len - 1, then the uncond row s_len further on
+        byte = (off + s_len - 1) * d * 2  # row off + s_len - 1, then the uncond row s_len further on
         lib = self.lib
-        _lib.check(lib.zmi_add_layernorm(self.hid_pre.data_ptr() + off, s_len * d, self.x_pre.data_ptr() + off,
+        _lib.check(lib.zmi_add_layernorm(self.hid_pre.data_ptr() + byte, s_len * d, self.x_pre.data_ptr() + byte,
                                          s_len * d, 2, d, self.w["nf_w"].data_ptr(), self.w["nf_b"].data_ptr(),
                                          self.eps, self.x_last.data_ptr(), d, 0, self.sptr), "norm_f")
         self._run_gemv(self._gemv(self.w["heads"], self.x_last, 2, HEADS_N_PAD, d, _lib.EPI_LOGITS, self.logits_pre,
