@@ -21,7 +21,8 @@ Two layers, so that a failure says which half is wrong:
              boundary, tests/test_gemv_cases_cpu.py).
 
 zmi_layernorm_rows against an fp64 LayerNorm: every element within 1 bf16 ulp of the fp64 value, no share (fp32 two-pass
-statistics can only flip a rounding; measured 0.50 ulp).
+statistics can only flip a rounding; measured 0.50 ulp). The same rule holds zmi_add_layernorm and zmi_gated_rmsnorm to
+addln_ref and grms_ref (tests/test_gpu_rownorm.py).
 """
 from __future__ import annotations
 
@@ -319,6 +320,20 @@ def layernorm_ref(X, w, b):
     mean = x.mean(dim=-1, keepdim=True)
     var = ((x - mean) ** 2).mean(dim=-1, keepdim=True)
     ref = (x - mean) / torch.sqrt(var + EPS) * w64 + b64
+    return ref, bf16_ulp(ref)
+
+
+def addln_ref(X, R, w, b):
+    """fp64 add + LayerNorm (layer_norm_fn, prenorm): layernorm_ref on the fp64 sum of the two bf16 inputs."""
+    return layernorm_ref(X.double() + R.double(), w, b)
+
+
+def grms_ref(Y, Z, w):
+    """fp64 RMSNormGated (norm_before_gate=False): g = y z sigmoid(z), out = g / sqrt(mean(g^2) + eps) w, and its
+    tolerance: 1 bf16 ulp of each value."""
+    z = Z.double()
+    g = Y.double() * z * torch.sigmoid(z)
+    ref = g / torch.sqrt((g * g).mean(dim=-1, keepdim=True) + EPS) * w.double()
     return ref, bf16_ulp(ref)
 
 

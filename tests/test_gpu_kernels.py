@@ -174,7 +174,7 @@ def _batch_invariant_production_shape(L, name):
 @pytest.mark.parametrize("K,M", [(2048, 2), (2048, 16), (2048, 37), (512, 5), (1024, 3)])
 def test_layernorm_rows_equals_gemv_prologue(K, M):
     """zmi_layernorm_rows (norm_f of the backbone plugin) and the GEMV LayerNorm prologue share one
-    arithmetic (zmi_common.h): a plain GEMV of the normalised rows equals the LayerNorm'd GEMV."""
+    arithmetic (zmi_rownorm.h): a plain GEMV of the normalised rows equals the LayerNorm'd GEMV."""
     L = _lib()
     N = 256
     W, X = rnd(N, K, scale=0.05, seed=14), rnd(M, K, scale=3.0, seed=15)

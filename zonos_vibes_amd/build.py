@@ -15,11 +15,11 @@ INCLUDE = os.path.join(REPO, "include")
 LIB = os.path.join(HERE, "libzonos_hip.so")
 SOURCES = ["zmi_gemv.hip"] + [f"zmi_gemv_e{i}.hip" for i in range(6)] + ["zmi_attn.hip", "zmi_attn_prefill.hip", "zmi_attnblk.hip", "zmi_sample.hip",
                                                                         "zmi_dac.hip", "zmi_misc.hip", "zmi_cond.hip",
-                                                                        "zmi_mamba.hip", "zmi_mambablk.hip",
+                                                                        "zmi_mamba.hip", "zmi_mambablk.hip", "zmi_rownorm.hip",
                                                                         "zmi_gemm_splitk.hip", "zmi_spk.hip", "zmi_pcm.hip",
                                                                         "zmi_resample.hip"]
 HEADERS = ["zmi_common.h", "zmi_kernels.h", "zmi_gemv_impl.h", "zmi_gemv_row.h", "zmi_attn_merge.h", "zmi_attn_ds.h", "zmi_mamba_step.h",
-           "zmi_prefetch.h"]
+           "zmi_prefetch.h", "zmi_rownorm.h"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unused-result",
          f"-I{INCLUDE}", f"-I{CSRC}"]

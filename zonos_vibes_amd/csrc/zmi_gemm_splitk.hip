@@ -124,18 +124,18 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* part, i
 }
 
 // The same reduce + residual for rows of 2048 columns, then the LayerNorm of each new row into `xn` (the next
-// op's prologue, zmi_layernorm_rows' arithmetic: part q = wave q, lane L's chunk at q 512 + 8 L, parts combined
-// (p0 + p1) + (p2 + p3), two passes): one 4-wave workgroup per row, so the next layer's LayerNorm pre-pass launch
+// op's prologue, zmi_rownorm.h's LayerNorm as in zmi_layernorm_rows: part q = wave q, one chunk per lane, two
+// passes): one 4-wave workgroup per row, so the next layer's LayerNorm pre-pass launch
 // is not needed.
 template <int NSEG>
 __global__ __launch_bounds__(256) void splitk_reduce_ln_kernel(const float* part, int M, bf16_t* out, int ldo,
                                                                const bf16_t* lw, const bf16_t* lb, float eps,
                                                                bf16_t* xn, int ldn) {
   constexpr int N = 2048, NQ = ln_parts(N);
-  static_assert(NQ == 4, "one wave per LayerNorm part");
+  static_assert(NQ == 4 && ln_chunks(N) == 1, "one wave per LayerNorm part, one chunk per lane");
   __shared__ float ps[2][NQ];
   const int m = blockIdx.x, t = threadIdx.x, lane = t & 63, q = t >> 6;
-  const int e0 = q * 512 + lane * 8;
+  const int e0 = ln_chunk_off(N, q, lane, 0);
   bf16_t* orow = out + (size_t)m * ldo;
   const uint4 xv = *reinterpret_cast<const uint4*>(orow + e0);
   const uint4 gw = *reinterpret_cast<const uint4*>(lw + e0), gb = *reinterpret_cast<const uint4*>(lb + e0);

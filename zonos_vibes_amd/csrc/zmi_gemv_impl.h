@@ -25,6 +25,7 @@
 #include "zmi_common.h"
 #include "zmi_kernels.h"
 #include "zmi_gemv_row.h"
+#include "zmi_rownorm.h"
 
 namespace zmi_gemv {
 
@@ -80,33 +81,6 @@ struct Img {
 };
 template <int K>
 using View = typename Img<K>::View;
-
-// fp32 sum of one 8-element chunk of x + aux (ADDLN: layer_norm_fn's fp32 residual sum), or of its
-// squared deviations; pairs added as (a + b), the order of ln_chunk_sum and zmi_add_layernorm
-__device__ __forceinline__ float addln_chunk_sum(const uint4& hv, const uint4& rv, float mean, bool sq) {
-  const uint32_t h[4] = {hv.x, hv.y, hv.z, hv.w}, r[4] = {rv.x, rv.y, rv.z, rv.w};
-  float t = 0.f;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float s0 = bf2f(h[j]) + bf2f(r[j]), s1 = bf2f(h[j] >> 16) + bf2f(r[j] >> 16);
-    if (sq) {
-      const float d0 = s0 - mean, d1 = s1 - mean;
-      t += d0 * d0 + d1 * d1;
-    } else {
-      t += s0 + s1;
-    }
-  }
-  return t;
-}
-// RMSNormGated's g = y * gate of element e of a chunk (fp32; gate = z * sigmoid(z), zmi_mamba2_step), the
-// value zmi_gated_rmsnorm forms as y * (z * sigmoid(z))
-__device__ __forceinline__ float gate_elem(const uint32_t (&y)[4], const float (&gz)[8], int e) {
-  return bf2f(y[e >> 1] >> (16 * (e & 1))) * gz[e];
-}
-__device__ __forceinline__ void load_gate(const float* p, float (&gz)[8]) {
-  const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
-  gz[0] = a.x; gz[1] = a.y; gz[2] = a.z; gz[3] = a.w; gz[4] = b.x; gz[5] = b.y; gz[6] = b.z; gz[7] = b.w;
-}
 
 // Diagnostic build only (-DZMI_GEMV_STAMPS, tools/gemv_stamps.py): thread 0 of every workgroup
 // writes s_memrealtime (100 MHz) at phase boundaries into diag[reserved][block][8].
@@ -401,7 +375,7 @@ __device__ __forceinline__ unsigned gather_attention_rows(const ZmiGemvArgs& a, 
   return act_rows;
 }
 
-// (3) The normalisation prologues (zmi_common.h arithmetic): task (row, part) per wave, so the few rows of a decode
+// (3) The normalisation prologues (zmi_rownorm.h arithmetic): task (row, part) per wave, so the few rows of a decode
 // step use every wave; partial sums meet in the segment-sum area `part` (free until the MFMA chain); each pass re-reads
 // its chunks from LDS (no row copy in VGPRs: the weight slice in flight already holds 4 NL of them, and occupancy
 // decides whether every workgroup of a wide GEMV is resident at once). One wave per row with no barriers between the
@@ -412,18 +386,18 @@ __device__ __forceinline__ unsigned gather_attention_rows(const ZmiGemvArgs& a, 
 // addln_chunk_sum of x + aux. A workgroup barrier after each pass.
 template <int K, int RT, int NWV, bool ADD>
 __device__ __forceinline__ void ln_statistics(const ZmiGemvArgs& a, const View<K>& L, int rows, int wave, int lane) {
-  constexpr int XROW = Img<K>::XROW, NQ = ln_parts(K), CPQ = K / (512 * NQ);
+  constexpr int XROW = Img<K>::XROW, NQ = ln_parts(K), CPQ = ln_chunks(K);
   float* part = L.red;
   const int ntask = rows * NQ;
   auto pass = [&](int task, float mean, bool sq) {
     const int r = task / NQ, q = task - r * NQ;
-    const int off = r * XROW + q * (K / NQ) + lane * 8;
     float t = 0.f;
 #pragma unroll
     for (int i = 0; i < CPQ; ++i) {
-      const uint4 xv = *reinterpret_cast<const uint4*>(L.xs + off + 512 * i);
+      const int off = r * XROW + ln_chunk_off(K, q, lane, i);
+      const uint4 xv = ld_chunk(L.xs + off);
       if constexpr (ADD)
-        t += addln_chunk_sum(xv, *reinterpret_cast<const uint4*>(L.xa + off + 512 * i), mean, sq);
+        t += addln_chunk_sum(xv, ld_chunk(L.xa + off), mean, sq);
       else
         t += ln_chunk_sum(xv, mean, sq);
     }
@@ -451,19 +425,17 @@ __device__ __forceinline__ void ln_statistics(const ZmiGemvArgs& a, const View<K
 // LayerNorm (nn.LayerNorm): x * rstd + nbias through ln_apply, in place
 template <int K, int RT, int NWV>
 __device__ __forceinline__ void prologue_layernorm(const ZmiGemvArgs& a, const View<K>& L, int rows, int wave, int lane) {
-  constexpr int XROW = Img<K>::XROW, NQ = ln_parts(K), CPQ = K / (512 * NQ);
+  constexpr int XROW = Img<K>::XROW, NQ = ln_parts(K), CPQ = ln_chunks(K);
   ln_statistics<K, RT, NWV, false>(a, L, rows, wave, lane);  // L.red: the parts' sums, then their squared deviations
   for (int task = wave; task < rows * NQ; task += NWV) {
     const int r = task / NQ, q = task - r * NQ;
     const float mean = ln_combine<NQ>(L.red + r * NQ) / (float)K;
     const float rstd = 1.0f / sqrtf(ln_combine<NQ>(L.red + RT * NQ + r * NQ) / (float)K + a.eps), nbias = -mean * rstd;
-    bf16_t* xr = L.xs + r * XROW + q * (K / NQ);
 #pragma unroll
     for (int i = 0; i < CPQ; ++i) {
-      const int c = q * (K / NQ) / 8 + lane + 64 * i;
-      const uint4 xv = *reinterpret_cast<const uint4*>(xr + (lane + 64 * i) * 8);
-      *reinterpret_cast<uint4*>(xr + (lane + 64 * i) * 8) = ln_apply(
-          xv, *reinterpret_cast<const uint4*>(L.gam + c * 8), *reinterpret_cast<const uint4*>(L.bet + c * 8), rstd, nbias);
+      const int off = ln_chunk_off(K, q, lane, i);
+      bf16_t* xp = L.xs + r * XROW + off;
+      st_chunk(xp, ln_apply(ld_chunk(xp), ld_chunk(L.gam + off), ld_chunk(L.bet + off), rstd, nbias));
     }
   }
   __syncthreads();
@@ -474,74 +446,61 @@ __device__ __forceinline__ void prologue_layernorm(const ZmiGemvArgs& a, const V
 template <int K, int RT, int NWV>
 __device__ __forceinline__ void prologue_add_layernorm(const ZmiGemvArgs& a, const View<K>& L, int rows,
                                                        int row0, bool wres, int wave, int lane) {
-  constexpr int XROW = Img<K>::XROW, NQ = ln_parts(K), CPQ = K / (512 * NQ);
+  constexpr int XROW = Img<K>::XROW, NQ = ln_parts(K), CPQ = ln_chunks(K);
   ln_statistics<K, RT, NWV, true>(a, L, rows, wave, lane);  // L.red: the parts' sums, then their squared deviations
   for (int task = wave; task < rows * NQ; task += NWV) {
     const int r = task / NQ, q = task - r * NQ;
     const float mean = ln_combine<NQ>(L.red + r * NQ) / (float)K;
     const float rstd = 1.0f / sqrtf(ln_combine<NQ>(L.red + RT * NQ + r * NQ) / (float)K + a.eps);
-    bf16_t* hr = L.xs + r * XROW + q * (K / NQ);
-    const bf16_t* rr = L.xa + r * XROW + q * (K / NQ);
 #pragma unroll
     for (int i = 0; i < CPQ; ++i) {
-      const int c = q * (K / NQ) / 8 + lane + 64 * i;
-      const uint4 hv = *reinterpret_cast<const uint4*>(hr + (lane + 64 * i) * 8);
-      const uint4 rv = *reinterpret_cast<const uint4*>(rr + (lane + 64 * i) * 8);
-      const uint4 gw = *reinterpret_cast<const uint4*>(L.gam + c * 8), gbv = *reinterpret_cast<const uint4*>(L.bet + c * 8);
-      const uint32_t h[4] = {hv.x, hv.y, hv.z, hv.w}, rs[4] = {rv.x, rv.y, rv.z, rv.w};
-      const uint32_t uw[4] = {gw.x, gw.y, gw.z, gw.w}, ub[4] = {gbv.x, gbv.y, gbv.z, gbv.w};
-      uint32_t o[4], so[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float s0 = bf2f(h[j]) + bf2f(rs[j]), s1 = bf2f(h[j] >> 16) + bf2f(rs[j] >> 16);
-        const float y0 = ((s0 - mean) * rstd) * bf2f(uw[j]) + bf2f(ub[j]);
-        const float y1 = ((s1 - mean) * rstd) * bf2f(uw[j] >> 16) + bf2f(ub[j] >> 16);
-        o[j] = f2bf(y0) | (f2bf(y1) << 16);
-        so[j] = f2bf(s0) | (f2bf(s1) << 16);
-      }
-      *reinterpret_cast<uint4*>(hr + (lane + 64 * i) * 8) = uint4{o[0], o[1], o[2], o[3]};
-      if (wres)
-        reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(a.res_out) + (size_t)(row0 + r) * a.ld_aux)[c] =
-            uint4{so[0], so[1], so[2], so[3]};
+      const int off = ln_chunk_off(K, q, lane, i);
+      bf16_t* hp = L.xs + r * XROW + off;
+      const AddLnChunk o = addln_apply(ld_chunk(hp), ld_chunk(L.xa + r * XROW + off), ld_chunk(L.gam + off),
+                                       ld_chunk(L.bet + off), mean, rstd);
+      st_chunk(hp, o.y);
+      if (wres) st_chunk(reinterpret_cast<bf16_t*>(a.res_out) + (size_t)(row0 + r) * a.ld_aux + off, o.s);
     }
   }
   __syncthreads();
 }
 
 // RMSNormGated (norm_before_gate=False): g = y (z sigmoid(z)), out = g rstd w into the x rows; g recomputed in the
-// apply pass (the same bits), sums of g^2 element by element as zmi_gated_rmsnorm (PRO_GRMSG: g read from the aux
-// rows). A wave takes its (row, part) tasks two at a time (the second clamped, its results dropped): two independent
+// apply pass (the same bits), zmi_rownorm.h's chunk sums and apply as in zmi_gated_rmsnorm (PRO_GRMSG: g read from the
+// aux rows). A wave takes its (row, part) tasks two at a time (the second clamped, its results dropped): two independent
 // dependent-add chains in one straight-line body instead of one after the other (the K = 4096 out_proj has 4 waves
-// for 2 rows x 4 parts). One workgroup barrier between the passes.
+// for 2 rows x 4 parts). One workgroup barrier between the passes. The order of the loads (y, gamma, gate) is the
+// measured one: equivalent spellings that loaded the gate first moved the hybrid decode step by 0.3 %.
 template <int K, int RT, int NWV, int PRO>
 __device__ __forceinline__ void prologue_gated_rmsnorm(const ZmiGemvArgs& a, const View<K>& L, int rows,
                                                        int wave, int lane) {
-  constexpr int XROW = Img<K>::XROW, GROW = Img<K>::GROW, NQ = ln_parts(K), CPQ = K / (512 * NQ);
+  constexpr int XROW = Img<K>::XROW, GROW = Img<K>::GROW, NQ = ln_parts(K), CPQ = ln_chunks(K);
   float* part = L.red;
   const int ntask = rows * NQ;
+  // g of the chunk at `off` of row r: y * gate, or (GRMS_G) as the aux row holds it
+  auto load_g = [&](int r, int off, float (&g)[8]) {
+    uint32_t y[4] = {0u, 0u, 0u, 0u};
+    if constexpr (PRO == PRO_GRMS) {
+      const uint4 yv = *reinterpret_cast<const uint4*>(L.xs + r * XROW + off);
+      y[0] = yv.x; y[1] = yv.y; y[2] = yv.z; y[3] = yv.w;
+    }
+    float gz[8];
+    load_gate(L.xg + r * GROW + off, gz);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) g[e] = PRO == PRO_GRMSG ? gz[e] : gate_elem(y, gz, e);
+  };
   for (int task0 = wave; task0 < ntask; task0 += 2 * NWV) {
     float t[2];
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int task = min(task0 + u * NWV, ntask - 1);
       const int r = task / NQ, q = task - r * NQ;
-      const bf16_t* yr = L.xs + r * XROW + q * (K / NQ);
-      const float* zr = L.xg + r * GROW + q * (K / NQ);
       t[u] = 0.f;
 #pragma unroll
       for (int i = 0; i < CPQ; ++i) {
-        uint32_t y[4] = {0u, 0u, 0u, 0u};
-        if constexpr (PRO == PRO_GRMS) {
-          const uint4 yv = *reinterpret_cast<const uint4*>(yr + (lane + 64 * i) * 8);
-          y[0] = yv.x; y[1] = yv.y; y[2] = yv.z; y[3] = yv.w;
-        }
-        float gz[8];
-        load_gate(zr + (lane + 64 * i) * 8, gz);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float g = PRO == PRO_GRMSG ? gz[e] : gate_elem(y, gz, e);
-          t[u] += g * g;
-        }
+        float g[8];
+        load_g(r, ln_chunk_off(K, q, lane, i), g);
+        t[u] = grms_chunk_sq(g, t[u]);
       }
     }
 #pragma unroll
@@ -559,26 +518,13 @@ __device__ __forceinline__ void prologue_gated_rmsnorm(const ZmiGemvArgs& a, con
       const int task = min(task0 + u * NWV, ntask - 1);
       const int r = task / NQ, q = task - r * NQ;
       const float rstd = 1.0f / sqrtf(ln_combine<NQ>(part + r * NQ) / (float)K + a.eps);
-      const bf16_t* yr = L.xs + r * XROW + q * (K / NQ);
-      const float* zr = L.xg + r * GROW + q * (K / NQ);
 #pragma unroll
       for (int i = 0; i < CPQ; ++i) {
-        const int c = q * (K / NQ) / 8 + lane + 64 * i;
-        uint32_t y[4] = {0u, 0u, 0u, 0u};
-        if constexpr (PRO == PRO_GRMS) {
-          const uint4 yv = *reinterpret_cast<const uint4*>(yr + (lane + 64 * i) * 8);
-          y[0] = yv.x; y[1] = yv.y; y[2] = yv.z; y[3] = yv.w;
-        }
-        const uint4 gw = *reinterpret_cast<const uint4*>(L.gam + c * 8);
-        const uint32_t uw[4] = {gw.x, gw.y, gw.z, gw.w};
-        float gz[8];
-        load_gate(zr + (lane + 64 * i) * 8, gz);
-        auto gv = [&](int e) { return PRO == PRO_GRMSG ? gz[e] : gate_elem(y, gz, e); };
-        uint32_t o[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          o[j] = f2bf((gv(2 * j) * rstd) * bf2f(uw[j])) | (f2bf((gv(2 * j + 1) * rstd) * bf2f(uw[j] >> 16)) << 16);
-        res[u][i] = uint4{o[0], o[1], o[2], o[3]};
+        const int off = ln_chunk_off(K, q, lane, i);
+        const uint4 gw = *reinterpret_cast<const uint4*>(L.gam + off);
+        float g[8];
+        load_g(r, off, g);
+        res[u][i] = grms_apply(g, gw, rstd);
       }
     }
     // stores after both tasks' reads: the clamped duplicate task reads what the real one overwrites
@@ -587,9 +533,9 @@ __device__ __forceinline__ void prologue_gated_rmsnorm(const ZmiGemvArgs& a, con
       const int task = task0 + u * NWV;
       if (task < ntask) {
         const int r = task / NQ, q = task - r * NQ;
-        bf16_t* yr = L.xs + r * XROW + q * (K / NQ);
+        bf16_t* yr = L.xs + r * XROW;
 #pragma unroll
-        for (int i = 0; i < CPQ; ++i) *reinterpret_cast<uint4*>(yr + (lane + 64 * i) * 8) = res[u][i];
+        for (int i = 0; i < CPQ; ++i) *reinterpret_cast<uint4*>(yr + ln_chunk_off(K, q, lane, i)) = res[u][i];
       }
     }
   }

@@ -1,14 +1,14 @@
-// Hybrid backbone kernels (Zonos-v0.1-hybrid, BASELINE config C4), gfx950.
+// Mamba2 kernels of the hybrid backbone (Zonos-v0.1-hybrid, BASELINE config C4), gfx950: step, scans, SSD.
 //
 // Reference: zonos/backbone/_mamba_ssm.py:9-57 builds its layers with mamba-ssm 2.2.4's
 // `create_block` (absent from this image, so parity is unpinned; oracle/hybrid_cpu.py restates the
 // published algorithm). A decode step of one Mamba2 block is
 //
-//   hidden, residual = layer_norm_fn(hidden, norm.w, norm.b, residual, prenorm=True)  (Block.forward)
+//   hidden, residual = layer_norm_fn(hidden, norm.w, norm.b, residual, prenorm=True)  (Block.forward; zmi_rownorm.hip)
 //   zxbcdt = in_proj(hidden)                                                            (GEMV kernel)
 //   xBC    = silu(causal_conv1d_update(xBC, conv_state, conv1d.w, conv1d.b))            (mamba2_step)
 //   y      = selective_state_update(ssm_state, x, dt, A, B, C, D, dt_bias, softplus)    (mamba2_step)
-//   y      = RMSNormGated(y, z)                                                         (gated_rmsnorm)
+//   y      = RMSNormGated(y, z)                                                         (zmi_rownorm.hip)
 //   out    = out_proj(y)                                                                (GEMV kernel)
 //
 // and the prefill is the same block over a whole sequence (causal_conv1d_fn + mamba_chunk_scan_combined;
@@ -626,135 +626,6 @@ __global__ __launch_bounds__(SSD_NT) void mamba2_ssd_kernel(const ZmiMamba2Args 
   }
 }
 
-// Row reductions of the two norms below: one 256-thread workgroup per row; the row is cut into NW
-// contiguous parts (4, or K / 512 below K = 2048), wave w < NW owns part w, lane L its 8-element chunks
-// L + 64 i; fp32 sums in chunk order, DPP wave sums, parts combined as (p0 + p1) + (p2 + p3) (absent parts
-// add +0, exactly). A row's bits do not depend on M.
-template <int K>
-struct RowSplit {
-  static constexpr int NW = K >= 2048 ? 4 : K / 512;
-  static constexpr int CPL = K / (512 * NW);
-  static_assert(NW >= 1 && CPL >= 1 && NW * CPL * 512 == K, "row split");
-};
-__device__ __forceinline__ float block_sum4(float v, float* part) {
-  v = wave_sum(v);
-  const int wave = threadIdx.x >> 6;
-  __syncthreads();  // part[] may still be read by the previous reduction
-  if ((threadIdx.x & 63) == 0) part[wave] = v;
-  __syncthreads();
-  return (part[0] + part[1]) + (part[2] + part[3]);
-}
-
-// ---------------------------------------------------------------------------- add + LayerNorm
-// layer_norm_fn(x, w, b, residual, prenorm=True, residual_in_fp32=False) (mamba_ssm/ops/triton/
-// layer_norm.py): s = x + residual in fp32; residual_out = bf16(s); y = (s - mean) * rstd * w + b on the
-// fp32 sum (two-pass statistics).
-template <int K>
-__global__ __launch_bounds__(256) void add_ln_kernel(const bf16_t* hid, int ldh, bf16_t* res, int ldr,
-                                                     const bf16_t* w, const bf16_t* b, float eps, bf16_t* out, int ldo,
-                                                     int store_res) {
-  constexpr int NW = RowSplit<K>::NW, CPL = RowSplit<K>::CPL;
-  __shared__ float part[4];
-  const int r = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const bool on = wave < NW;
-  float v[CPL][8];
-  float sum = 0.f;
-#pragma unroll
-  for (int i = 0; i < CPL; ++i) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[i][e] = 0.f;
-    if (!on) continue;
-    const int c = wave * (K / (8 * NW)) + lane + 64 * i;  // 8-element chunk index in the row
-    const uint4 rv = reinterpret_cast<const uint4*>(res + (size_t)r * ldr)[c];
-    uint32_t u[4] = {rv.x, rv.y, rv.z, rv.w};
-    uint32_t hu[4] = {0u, 0u, 0u, 0u};
-    if (hid) {
-      const uint4 hv = reinterpret_cast<const uint4*>(hid + (size_t)r * ldh)[c];
-      hu[0] = hv.x; hu[1] = hv.y; hu[2] = hv.z; hu[3] = hv.w;
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      v[i][2 * e] = hid ? bf2f(hu[e]) + bf2f(u[e]) : bf2f(u[e]);
-      v[i][2 * e + 1] = hid ? bf2f(hu[e] >> 16) + bf2f(u[e] >> 16) : bf2f(u[e] >> 16);
-      sum += v[i][2 * e] + v[i][2 * e + 1];
-    }
-    if (store_res && hid) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) u[e] = f2bf(v[i][2 * e]) | (f2bf(v[i][2 * e + 1]) << 16);
-      reinterpret_cast<uint4*>(res + (size_t)r * ldr)[c] = uint4{u[0], u[1], u[2], u[3]};
-    }
-  }
-  const float mean = block_sum4(sum, part) / (float)K;
-  float sq = 0.f;  // pairs as (a + b): the GEMV ADDLN prologue's order (zmi_gemv_impl.h addln_chunk_sum)
-#pragma unroll
-  for (int i = 0; i < CPL; ++i)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float d0 = v[i][2 * e] - mean, d1 = v[i][2 * e + 1] - mean;
-      sq += on ? d0 * d0 + d1 * d1 : 0.f;
-    }
-  const float rstd = 1.0f / sqrtf(block_sum4(sq, part) / (float)K + eps);
-  if (!on) return;
-#pragma unroll
-  for (int i = 0; i < CPL; ++i) {
-    const int c = wave * (K / (8 * NW)) + lane + 64 * i;
-    const uint4 gw = reinterpret_cast<const uint4*>(w)[c], gb = reinterpret_cast<const uint4*>(b)[c];
-    const uint32_t uw[4] = {gw.x, gw.y, gw.z, gw.w}, ub[4] = {gb.x, gb.y, gb.z, gb.w};
-    uint32_t o[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float y0 = ((v[i][2 * e] - mean) * rstd) * bf2f(uw[e]) + bf2f(ub[e]);
-      const float y1 = ((v[i][2 * e + 1] - mean) * rstd) * bf2f(uw[e] >> 16) + bf2f(ub[e] >> 16);
-      o[e] = f2bf(y0) | (f2bf(y1) << 16);
-    }
-    reinterpret_cast<uint4*>(out + (size_t)r * ldo)[c] = uint4{o[0], o[1], o[2], o[3]};
-  }
-}
-
-// ---------------------------------------------------------------------------- gated RMSNorm
-// RMSNormGated(norm_before_gate=False, one group) (mamba_ssm/ops/triton/layernorm_gated.py):
-// g = y * (z * sigmoid(z)) in fp32, out = g * rstd * w with rstd = 1 / sqrt(mean(g^2) + eps), bf16.
-template <int K>
-__global__ __launch_bounds__(256) void gated_rms_kernel(const bf16_t* y, int ldy, const bf16_t* z, int ldz,
-                                                        const bf16_t* w, float eps, bf16_t* out, int ldo) {
-  constexpr int NW = RowSplit<K>::NW, CPL = RowSplit<K>::CPL;
-  __shared__ float part[4];
-  const int r = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const bool on = wave < NW;
-  float g[CPL][8];
-  float sq = 0.f;
-#pragma unroll
-  for (int i = 0; i < CPL; ++i) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) g[i][e] = 0.f;
-    if (!on) continue;
-    const int c = wave * (K / (8 * NW)) + lane + 64 * i;
-    const uint4 yv = reinterpret_cast<const uint4*>(y + (size_t)r * ldy)[c];
-    const uint4 zv = reinterpret_cast<const uint4*>(z + (size_t)r * ldz)[c];
-    const uint32_t uy[4] = {yv.x, yv.y, yv.z, yv.w}, uz[4] = {zv.x, zv.y, zv.z, zv.w};
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float zz = bf2f(uz[e >> 1] >> (16 * (e & 1)));
-      const float sg = 1.0f / (1.0f + expf(-zz));
-      g[i][e] = bf2f(uy[e >> 1] >> (16 * (e & 1))) * (zz * sg);
-      sq += g[i][e] * g[i][e];
-    }
-  }
-  const float rstd = 1.0f / sqrtf(block_sum4(sq, part) / (float)K + eps);
-  if (!on) return;
-#pragma unroll
-  for (int i = 0; i < CPL; ++i) {
-    const int c = wave * (K / (8 * NW)) + lane + 64 * i;
-    const uint4 gw = reinterpret_cast<const uint4*>(w)[c];
-    const uint32_t uw[4] = {gw.x, gw.y, gw.z, gw.w};
-    uint32_t o[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      o[e] = f2bf((g[i][2 * e] * rstd) * bf2f(uw[e])) | (f2bf((g[i][2 * e + 1] * rstd) * bf2f(uw[e] >> 16)) << 16);
-    reinterpret_cast<uint4*>(out + (size_t)r * ldo)[c] = uint4{o[0], o[1], o[2], o[3]};
-  }
-}
-
 int check_mamba(const ZmiMamba2Args* a) {
   if (!a || !a->zxbcdt || !a->conv_w || !a->conv_b || !a->dt_bias || !a->A || !a->D || !a->conv_ring || !a->ssm ||
       !a->y || !a->row_pos)
@@ -890,47 +761,4 @@ extern "C" int zmi_mamba2_scan_seqs(const ZmiMamba2Args* a, const ZmiAttnSeq* se
     return zmi_fail_msg("mamba2_scan_seqs: workspace smaller than zmi_mamba2_scan_ws_bytes");
   if (rows.empty()) return 0;
   return launch_scan(a, ScanSeqs{seqs, n_seq, 0, 0, 0}, n_ssd, t_max, n_scan, pq, ws, (hipStream_t)stream);
-}
-
-extern "C" int zmi_add_layernorm(const void* hidden, int ldh, void* residual, int ldr, int m, int k, const void* w,
-                                 const void* b, float eps, void* out, int ldo, int store_residual, void* stream) {
-  if (ldh % 8 || ldr % 8 || ldo % 8) return zmi_fail_msg("add_layernorm: leading dimensions must be multiples of 8");
-  if (!residual || !w || !b || !out) return zmi_fail_msg("add_layernorm: missing buffers");
-  if (m <= 0) return 0;
-  const dim3 grid((unsigned)m);
-  hipStream_t s = (hipStream_t)stream;
-#define ZMI_ADDLN(KK)                                                                                         \
-  hipLaunchKernelGGL(add_ln_kernel<KK>, grid, dim3(256), 0, s, (const bf16_t*)hidden, ldh, (bf16_t*)residual, \
-                     ldr, (const bf16_t*)w, (const bf16_t*)b, eps, (bf16_t*)out, ldo, store_residual)
-  switch (k) {
-    case 512: ZMI_ADDLN(512); break;
-    case 1024: ZMI_ADDLN(1024); break;
-    case 2048: ZMI_ADDLN(2048); break;
-    case 4096: ZMI_ADDLN(4096); break;
-    default: return zmi_fail_msg("add_layernorm: k must be 512, 1024, 2048 or 4096");
-  }
-#undef ZMI_ADDLN
-  ZMI_CHECK(hipGetLastError());
-  return 0;
-}
-
-extern "C" int zmi_gated_rmsnorm(const void* y, int ldy, const void* z, int ldz, int m, int k, const void* w,
-                                 float eps, void* out, int ldo, void* stream) {
-  if (ldy % 8 || ldz % 8 || ldo % 8) return zmi_fail_msg("gated_rmsnorm: leading dimensions must be multiples of 8");
-  if (!y || !z || !w || !out) return zmi_fail_msg("gated_rmsnorm: missing buffers");
-  if (m <= 0) return 0;
-  hipStream_t s = (hipStream_t)stream;
-#define ZMI_GRMS(KK)                                                                                          \
-  hipLaunchKernelGGL(gated_rms_kernel<KK>, dim3((unsigned)m), dim3(256), 0, s, (const bf16_t*)y, ldy,         \
-                     (const bf16_t*)z, ldz, (const bf16_t*)w, eps, (bf16_t*)out, ldo)
-  switch (k) {
-    case 512: ZMI_GRMS(512); break;
-    case 1024: ZMI_GRMS(1024); break;
-    case 2048: ZMI_GRMS(2048); break;
-    case 4096: ZMI_GRMS(4096); break;
-    default: return zmi_fail_msg("gated_rmsnorm: k must be 512, 1024, 2048 or 4096");
-  }
-#undef ZMI_GRMS
-  ZMI_CHECK(hipGetLastError());
-  return 0;
 }

@@ -3,6 +3,7 @@
 #pragma once
 #include "zmi_common.h"
 #include "zmi_kernels.h"
+#include "zmi_rownorm.h"
 
 namespace zmi_mamba {
 
@@ -143,10 +144,9 @@ __device__ __forceinline__ void step_core(const ZmiMamba2Args& a, int m, int h, 
     const uint32_t yb = f2bf(out + x * pre.D);
     reinterpret_cast<bf16_t*>(a.y)[(size_t)m * a.ldy + h * MB_HD + p] = (bf16_t)yb;
     if (a.gz) {  // RMSNormGated's gate of this channel, once (the out_proj GEMV's GRMS prologue multiplies), or (gz_g)
-                 // g = y * gate itself, the product gate_elem forms (GRMS_G: the out_proj then stages no y rows)
-      const float zz = bf2f(raw[RAW_Z + p]);
-      const float gate = zz * (1.0f / (1.0f + expf(-zz)));
-      a.gz[(size_t)m * a.ldy + h * MB_HD + p] = a.gz_g ? bf2f(yb) * gate : gate;
+                 // g = y * gate itself, zmi_rownorm.h's product (GRMS_G: the out_proj then stages no y rows)
+      const float gate = gate_of(bf2f(raw[RAW_Z + p]));
+      a.gz[(size_t)m * a.ldy + h * MB_HD + p] = a.gz_g ? gated(bf2f(yb), gate) : gate;
     }
   }
 }

@@ -125,74 +125,3 @@ extern "C" int zmi_graph_destroy(void* graph_exec) {
   if (graph_exec) ZMI_CHECK(hipGraphExecDestroy((hipGraphExec_t)graph_exec));
   return 0;
 }
-
-// ---- LayerNorm of whole rows (nn.LayerNorm, reference zonos/backbone/_torch.py:62,88,90) -------------
-// One wave per row, the parts of zmi_common.h's LayerNorm arithmetic in order (the GEMV prologue spreads
-// the same parts over waves: identical bits), bf16 output. Used for norm_f by the backbone plugin
-// (zonos_vibes_amd/backbone.py); the decode step fuses its LayerNorms.
-namespace {
-template <int CPL>
-__global__ __launch_bounds__(256) void layernorm_rows_kernel(const bf16_t* x, int ldx, int m, const bf16_t* w,
-                                                             const bf16_t* b, float eps, bf16_t* out, int ldo) {
-  constexpr int K = CPL * 512, NQ = ln_parts(K), CPQ = CPL / NQ;
-  const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (r >= m) return;
-  const bf16_t* xr = x + (size_t)r * ldx;
-  uint4 xv[NQ][CPQ], gw[NQ][CPQ], gb[NQ][CPQ];
-  float p[NQ];
-  // the row, gamma and beta loads all in flight together (one memory round trip, not two)
-#pragma unroll
-  for (int q = 0; q < NQ; ++q)
-#pragma unroll
-    for (int i = 0; i < CPQ; ++i) {
-      const int c = q * (K / NQ) / 8 + lane + 64 * i;
-      xv[q][i] = *reinterpret_cast<const uint4*>(xr + q * (K / NQ) + (lane + 64 * i) * 8);
-      gw[q][i] = reinterpret_cast<const uint4*>(w)[c];
-      gb[q][i] = reinterpret_cast<const uint4*>(b)[c];
-    }
-#pragma unroll
-  for (int q = 0; q < NQ; ++q) {
-    float t = 0.f;
-#pragma unroll
-    for (int i = 0; i < CPQ; ++i) t += ln_chunk_sum(xv[q][i], 0.f, false);
-    p[q] = wave_sum(t);
-  }
-  const float mean = ln_combine<NQ>(p) / (float)K;
-#pragma unroll
-  for (int q = 0; q < NQ; ++q) {
-    float t = 0.f;
-#pragma unroll
-    for (int i = 0; i < CPQ; ++i) t += ln_chunk_sum(xv[q][i], mean, true);
-    p[q] = wave_sum(t);
-  }
-  const float rstd = 1.0f / sqrtf(ln_combine<NQ>(p) / (float)K + eps), nbias = -mean * rstd;
-#pragma unroll
-  for (int q = 0; q < NQ; ++q)
-#pragma unroll
-    for (int i = 0; i < CPQ; ++i) {
-      const int c = q * (K / NQ) / 8 + lane + 64 * i;
-      reinterpret_cast<uint4*>(out + (size_t)r * ldo)[c] = ln_apply(xv[q][i], gw[q][i], gb[q][i], rstd, nbias);
-    }
-}
-}  // namespace
-
-extern "C" int zmi_layernorm_rows(const void* x, int ldx, int m, int k, const void* w, const void* b, float eps,
-                                  void* out, int ldo, void* stream) {
-  if (ldx % 8 || ldo % 8) return zmi_fail_msg("layernorm_rows: ldx and ldo must be multiples of 8");
-  if (m <= 0) return 0;
-  const dim3 grid((m + 3) / 4);
-  hipStream_t s = (hipStream_t)stream;
-  switch (k) {
-    case 512: hipLaunchKernelGGL(layernorm_rows_kernel<1>, grid, dim3(256), 0, s, (const bf16_t*)x, ldx, m,
-                                 (const bf16_t*)w, (const bf16_t*)b, eps, (bf16_t*)out, ldo); break;
-    case 1024: hipLaunchKernelGGL(layernorm_rows_kernel<2>, grid, dim3(256), 0, s, (const bf16_t*)x, ldx, m,
-                                  (const bf16_t*)w, (const bf16_t*)b, eps, (bf16_t*)out, ldo); break;
-    case 2048: hipLaunchKernelGGL(layernorm_rows_kernel<4>, grid, dim3(256), 0, s, (const bf16_t*)x, ldx, m,
-                                  (const bf16_t*)w, (const bf16_t*)b, eps, (bf16_t*)out, ldo); break;
-    case 4096: hipLaunchKernelGGL(layernorm_rows_kernel<8>, grid, dim3(256), 0, s, (const bf16_t*)x, ldx, m,
-                                  (const bf16_t*)w, (const bf16_t*)b, eps, (bf16_t*)out, ldo); break;
-    default: return zmi_fail_msg("layernorm_rows: k must be 512, 1024, 2048 or 4096");
-  }
-  ZMI_CHECK(hipGetLastError());
-  return 0;
-}

@@ -6,7 +6,7 @@ around the backbone — delay pattern, prefill orchestration, heads, CFG, sample
 hipGraph-captured decode loop, slots — is HipEngine's; this class only swaps the layer plan:
 
   every block    layer_norm_fn prenorm (residual += hidden in fp32, LayerNorm): decode as the ADDLN
-                 prologue of the block's first GEMV, prefill as zmi_add_layernorm (same arithmetic)
+                 prologue of the block's first GEMV, prefill as zmi_add_layernorm (both on csrc/zmi_rownorm.h's arithmetic)
   Mamba2 block   zmi_mamba_block: in_proj GEMV + the Mamba2 step (conv ring + SiLU + selective state
                  update) in one launch, granule hand-off (zmi_mamba2_step as its own launch above 16 rows)
                  -> out_proj GEMV with the GRMS prologue (RMSNormGated; prefill: zmi_gated_rmsnorm and
