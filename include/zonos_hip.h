@@ -247,11 +247,22 @@ typedef struct ZmiSlots {
   const int* total_len; /* [S] delayed length P + N + 9 (frames at or past it are not written) */
   int tcap;
   int n_slots;
+  int rows_per_slot; /* the row layout of zmi_sample_step (modes 0, 1), zmi_sample_step_greedy and zmi_embed_step:
+                      * 0 or 2 = paired: slot s owns logits / activation / KV rows 2s (conditional) and 2s + 1
+                      *          (unconditional), the CFG pair of model.py:142; the score is u + (c - u) * cfg_scale;
+                      * 1      = single (guidance-free generation, the reference's cfg_scale == 1: model.py:112,
+                      *          134-136, 193): slot s owns row s, the score is that row's logit as it is
+                      *          (ZmiSampling.cfg_scale is ignored, no second row is read), the kernels write
+                      *          row_kv[s] = s, row_pos[s] and x[s] and touch nothing of rows >= n_slots;
+                      * anything else is an error before any launch. A zero-initialised trailing field, so a caller
+                      * that fills the eleven fields above keeps the paired layout (zmi_version 10). */
 } ZmiSlots;
 
 /* mode 0 = decode step (bias + penalty + FSM), 1 = prefill (no bias, no penalty, no FSM).
  * With emb != NULL the slot's next input frame is embedded in the same launch (x[2s], x[2s+1],
- * model.py:97-98,142) and row_kv/row_pos (optional) receive the next step's KV row / position. */
+ * model.py:97-98,142; single layout: x[s]) and row_kv/row_pos (optional) receive the next step's KV row / position.
+ * Everything after the score (column 1025 = -inf, EOS bias, penalty, sampling, the EOS state machine, the frame
+ * write, the noise counters) is the same code in both layouts. */
 int zmi_sample_step(const ZmiSlots* slots, const float* logits_rows, const float* noise, int* next_tokens,
                     unsigned* counters, int mode, int slot_begin, int slot_count, const void* emb, int d, void* x,
                     int* row_kv, int* row_pos, void* stream);
@@ -268,7 +279,7 @@ int zmi_sample_logits(const float* logits, const int* generated, int gen_len, in
  * (apply: out [batch][9][T + 9]; revert: T >= 9, out [batch][9][T - 9]). */
 int zmi_apply_delay_pattern(const int64_t* codes, int64_t* out, int batch, int T, int64_t mask_token, void* stream);
 int zmi_revert_delay_pattern(const int64_t* codes, int64_t* out, int batch, int T, void* stream);
-/* x[2s], x[2s+1] = sum_k emb_k[delayed[s][k][offset[s]]]  (model.py:97-98,142) and the
+/* x[2s], x[2s+1] = sum_k emb_k[delayed[s][k][offset[s]]]  (model.py:97-98,142; single layout: x[s]) and the
  * per-row (kv row, position) tables of the step (-1 position for inactive slots). */
 int zmi_embed_step(const ZmiSlots* slots, const void* emb, int d, void* x, int* row_kv, int* row_pos,
                    void* stream);

@@ -78,6 +78,7 @@ class Slots(ctypes.Structure):
         ("active", c_void_p), ("pos", c_void_p), ("offset", c_void_p), ("remaining", c_void_p),
         ("stopping", c_void_p), ("step", c_void_p), ("delayed", c_void_p), ("params", c_void_p),
         ("total_len", c_void_p), ("tcap", c_int), ("n_slots", c_int),
+        ("rows_per_slot", c_int),  # 0 / 2: paired rows 2s, 2s + 1 (CFG); 1: one row per slot (guidance-free)
     ]
 
 
@@ -235,7 +236,7 @@ _SIGS = {
 
 EXPORTED = sorted(_SIGS)
 _lib = None
-ABI_VERSION = 9  # zmi_version() of the library this binding (and its weight packers) is written for
+ABI_VERSION = 10  # zmi_version() of the library this binding (and its weight packers) is written for
 
 
 def load(path: str = LIB_PATH) -> ctypes.CDLL:

@@ -2,6 +2,7 @@
 //
 // One workgroup per (codebook, slot) computes, over the 1026-entry vocabulary:
 //   CFG            u + (c - u) * cfg, column 1025 = -inf          reference model.py:112-115
+//                  (single layout, ZmiSlots.rows_per_slot == 1: the slot's one logits row as it is, model.py:112)
 //   EOS bias       -inf on EOS for codebooks 1..8 (decode only)    model.py:266-267,280
 //   rep. penalty   penalty^count over generated[..., -window:]   sampling.py:99-114,164-165 (any window)
 //   greedy         argmax, first index on ties                      sampling.py:180
@@ -163,6 +164,10 @@ __device__ void softmax_inplace(float* x, float* red) {
   __syncthreads();
 }
 
+// RPS: logits / activation rows per slot, a compile-time layout. 2: slot s owns rows 2s (conditional) and 2s + 1
+// (unconditional) and scores u + (c - u) * cfg. 1: slot s owns row s, the score is the row's logit (no CFG
+// arithmetic, cfg_scale ignored, no load of a second row). Mode 2 (no slots) runs in the RPS = 2 instantiation.
+template <int RPS>
 __global__ __launch_bounds__(SORT_THREADS) void sample_kernel(const SampleArgs a) {
   __shared__ float probs[NV + 2];
   __shared__ int cnt[NV];
@@ -178,9 +183,9 @@ __global__ __launch_bounds__(SORT_THREADS) void sample_kernel(const SampleArgs a
   const int s = alone ? blockIdx.y : a.slot_begin + blockIdx.y;
   if (!alone && !a.sl.active[s]) return;
   const ZmiSampling P = alone ? *a.params1 : a.sl.params[s];
-  const int lrow = alone ? blockIdx.y : 2 * blockIdx.y;
+  const int lrow = alone ? blockIdx.y : RPS * blockIdx.y;
   const float* lc = a.logits + ((size_t)lrow * ZMI_NCB + cb) * NV;
-  const float* lu = alone ? lc : a.logits + ((size_t)(lrow + 1) * ZMI_NCB + cb) * NV;
+  const float* lu = (alone || RPS == 1) ? lc : a.logits + ((size_t)(lrow + 1) * ZMI_NCB + cb) * NV;
   const bool decode = a.mode == 0;
   const int* dl = alone ? a.gen + ((size_t)s * ZMI_NCB + cb) * a.gen_len
                         : a.sl.delayed + ((size_t)s * ZMI_NCB + cb) * a.sl.tcap;
@@ -202,14 +207,19 @@ __global__ __launch_bounds__(SORT_THREADS) void sample_kernel(const SampleArgs a
   for (int i = 0; i < PER; ++i) {  // all logit loads in flight together (clamped index)
     const int v = min(t + i * 256, NV - 1);
     cv[i] = lc[v];
-    uv[i] = lu[v];
+    if constexpr (RPS == 2) uv[i] = lu[v];
   }
 #pragma unroll
   for (int i = 0; i < PER; ++i) {
     const int v = t + i * 256;
     if (v >= NV) break;
-    const float c = cv[i], u = uv[i];
-    float l = alone ? c : u + (c - u) * P.cfg_scale;
+    float l;
+    if constexpr (RPS == 2) {
+      const float c = cv[i], u = uv[i];
+      l = alone ? c : u + (c - u) * P.cfg_scale;
+    } else {
+      l = cv[i];
+    }
     if (v >= 1025) l = -INFINITY;
     if (decode) l = l + ((cb >= 1 && v == ZMI_EOS) ? -INFINITY : 0.0f);
     if (pen) {  // factor = penalty^count as the reference's scatter_reduce(prod) builds it
@@ -385,18 +395,27 @@ __global__ __launch_bounds__(SORT_THREADS) void sample_kernel(const SampleArgs a
       }
     }
     frame[ZMI_NCB] = act;
-    if (a.row_pos) {  // (kv row, position) of the next step's CFG pair
-      a.row_kv[2 * s] = 2 * s;
-      a.row_kv[2 * s + 1] = 2 * s + 1;
-      a.row_pos[2 * s] = act ? pos : -1;
-      a.row_pos[2 * s + 1] = act ? pos : -1;
+    if (a.row_pos) {  // (kv row, position) of the next step's CFG pair (single layout: of the slot's one row)
+      if constexpr (RPS == 2) {
+        a.row_kv[2 * s] = 2 * s;
+        a.row_kv[2 * s + 1] = 2 * s + 1;
+        a.row_pos[2 * s] = act ? pos : -1;
+        a.row_pos[2 * s + 1] = act ? pos : -1;
+      } else {
+        a.row_kv[s] = s;
+        a.row_pos[s] = act ? pos : -1;
+      }
     }
   }
-  // ---- next step's input embedding: x[2s] = x[2s+1] = sum_k emb_k[frame_k]  (model.py:97-98,142)
+  // ---- next step's input embedding: x[2s] = x[2s+1] = sum_k emb_k[frame_k]  (model.py:97-98,142); single: x[s]
   if (a.emb) {
     __syncthreads();
-    if (frame[ZMI_NCB])
-      embed_row(frame, a.emb, a.d, a.x + (size_t)(2 * s) * a.d, a.x + (size_t)(2 * s + 1) * a.d);
+    if (frame[ZMI_NCB]) {
+      if constexpr (RPS == 2)
+        embed_row(frame, a.emb, a.d, a.x + (size_t)(2 * s) * a.d, a.x + (size_t)(2 * s + 1) * a.d);
+      else
+        embed_row(frame, a.emb, a.d, a.x + (size_t)s * a.d, nullptr);
+    }
   }
 }
 
@@ -406,6 +425,8 @@ __global__ __launch_bounds__(SORT_THREADS) void sample_kernel(const SampleArgs a
 // frame write and next-step embedding. Every load that does not depend on another (logits, slot state, the
 // penalty window, the frame cells) is issued at launch start, and there is no in-launch ticket between
 // codebook workgroups: the step's sampler is ~3 dependent memory round trips instead of ~7.
+// RPS as in sample_kernel; the single layout issues no load of an unconditional row.
+template <int RPS>
 __global__ __launch_bounds__(64 * ZMI_NCB) void sample_greedy_kernel(const SampleArgs a) {
   __shared__ int cnt[ZMI_NCB][NV];
   __shared__ int tokv[ZMI_NCB];
@@ -419,15 +440,16 @@ __global__ __launch_bounds__(64 * ZMI_NCB) void sample_greedy_kernel(const Sampl
   // behind that round trip (sampler 8.25 -> 8.09 us, profiles/r04_sampler_hoist_ab.jsonl). An inactive slot's
   // state is valid (its last utterance's), the penalty indices are clamped, and it leaves before any write.
   const int act0 = a.sl.active[s];
-  const int lrow = 2 * blockIdx.x;
+  const int lrow = RPS * blockIdx.x;
   const float2* lc = reinterpret_cast<const float2*>(a.logits + ((size_t)lrow * ZMI_NCB + k) * NV);
-  const float2* lu = reinterpret_cast<const float2*>(a.logits + ((size_t)(lrow + 1) * ZMI_NCB + k) * NV);
+  const float2* lu =
+      RPS == 2 ? reinterpret_cast<const float2*>(a.logits + ((size_t)(lrow + 1) * ZMI_NCB + k) * NV) : lc;
   float2 cv[PP], uv[PP];
 #pragma unroll
   for (int i = 0; i < PP; ++i) {  // all logit loads in flight together (clamped index)
     const int p = min(lane + 64 * i, NP - 1);
     cv[i] = lc[p];
-    uv[i] = lu[p];
+    if constexpr (RPS == 2) uv[i] = lu[p];
   }
   const ZmiSampling P = a.sl.params[s];
   const int o = a.sl.offset[s] + 1;  // frames before the one sampled now
@@ -451,8 +473,13 @@ __global__ __launch_bounds__(64 * ZMI_NCB) void sample_greedy_kernel(const Sampl
     for (int h = 0; h < 2; ++h) {
       const int v = 2 * (lane + 64 * i) + h;
       if (v >= NV) break;
-      const float c = h ? cv[i].y : cv[i].x, u = h ? uv[i].y : uv[i].x;
-      float l = u + (c - u) * P.cfg_scale;
+      float l;
+      if constexpr (RPS == 2) {
+        const float c = h ? cv[i].y : cv[i].x, u = h ? uv[i].y : uv[i].x;
+        l = u + (c - u) * P.cfg_scale;
+      } else {
+        l = h ? cv[i].y : cv[i].x;
+      }
       if (v >= 1025) l = -INFINITY;
       l = l + ((k >= 1 && v == ZMI_EOS) ? -INFINITY : 0.0f);
       if (pen) {
@@ -516,18 +543,27 @@ __global__ __launch_bounds__(64 * ZMI_NCB) void sample_greedy_kernel(const Sampl
     const int act = rem > 0;
     if (!act) a.sl.active[s] = 0;
     frame[ZMI_NCB] = act;
-    if (a.row_pos) {  // (kv row, position) of the next step's CFG pair
-      a.row_kv[2 * s] = 2 * s;
-      a.row_kv[2 * s + 1] = 2 * s + 1;
-      a.row_pos[2 * s] = act ? pos : -1;
-      a.row_pos[2 * s + 1] = act ? pos : -1;
+    if (a.row_pos) {  // (kv row, position) of the next step's CFG pair (single layout: of the slot's one row)
+      if constexpr (RPS == 2) {
+        a.row_kv[2 * s] = 2 * s;
+        a.row_kv[2 * s + 1] = 2 * s + 1;
+        a.row_pos[2 * s] = act ? pos : -1;
+        a.row_pos[2 * s + 1] = act ? pos : -1;
+      } else {
+        a.row_kv[s] = s;
+        a.row_pos[s] = act ? pos : -1;
+      }
     }
   }
-  // ---- next step's input embedding: x[2s] = x[2s+1] = sum_k emb_k[frame_k]  (model.py:97-98,142)
+  // ---- next step's input embedding: x[2s] = x[2s+1] = sum_k emb_k[frame_k]  (model.py:97-98,142); single: x[s]
   if (a.emb) {
     __syncthreads();
-    if (frame[ZMI_NCB] && t < 256)
-      embed_row(frame, a.emb, a.d, a.x + (size_t)(2 * s) * a.d, a.x + (size_t)(2 * s + 1) * a.d);
+    if (frame[ZMI_NCB] && t < 256) {
+      if constexpr (RPS == 2)
+        embed_row(frame, a.emb, a.d, a.x + (size_t)(2 * s) * a.d, a.x + (size_t)(2 * s + 1) * a.d);
+      else
+        embed_row(frame, a.emb, a.d, a.x + (size_t)s * a.d, nullptr);
+    }
   }
 }
 
@@ -561,13 +597,14 @@ __device__ void embed_row(const int* toks, const bf16_t* emb, int d, bf16_t* out
   }
 }
 
+template <int RPS>
 __global__ __launch_bounds__(256) void embed_step_kernel(const ZmiSlots sl, const bf16_t* emb, int d, bf16_t* x,
                                                           int* row_kv, int* row_pos) {
   const int s = blockIdx.x;
   const int act = sl.active[s];
-  if (threadIdx.x < 2) {
-    row_kv[2 * s + threadIdx.x] = 2 * s + threadIdx.x;
-    row_pos[2 * s + threadIdx.x] = act ? sl.pos[s] : -1;
+  if (threadIdx.x < RPS) {
+    row_kv[RPS * s + threadIdx.x] = RPS * s + threadIdx.x;
+    row_pos[RPS * s + threadIdx.x] = act ? sl.pos[s] : -1;
   }
   if (!act) return;
   int toks[ZMI_NCB];
@@ -576,7 +613,10 @@ __global__ __launch_bounds__(256) void embed_step_kernel(const ZmiSlots sl, cons
     int tk = sl.delayed[((size_t)s * ZMI_NCB + k) * sl.tcap + off];
     toks[k] = tk < 0 ? 0 : (tk > ZMI_MASK ? ZMI_MASK : tk);
   }
-  embed_row(toks, emb, d, x + (size_t)(2 * s) * d, x + (size_t)(2 * s + 1) * d);
+  if constexpr (RPS == 2)
+    embed_row(toks, emb, d, x + (size_t)(2 * s) * d, x + (size_t)(2 * s + 1) * d);
+  else
+    embed_row(toks, emb, d, x + (size_t)s * d, nullptr);
 }
 
 __global__ __launch_bounds__(256) void embed_codes_kernel(const int* codes, int ld, const bf16_t* emb, int d,
@@ -632,6 +672,12 @@ __global__ void revert_delay_kernel(const int64_t* codes, int64_t* out, int T) {
   out[((size_t)b * ZMI_NCB + k) * (T - ZMI_NCB) + t] = codes[((size_t)b * ZMI_NCB + k) * T + t + k + 1];
 }
 
+// ZmiSlots.rows_per_slot -> the kernels' RPS: 0 or 2 the paired layout, 1 the single one, -1 anything else
+int slots_layout(const ZmiSlots* slots) {
+  const int r = slots->rows_per_slot;
+  return (r == 0 || r == 2) ? 2 : (r == 1 ? 1 : -1);
+}
+
 }  // namespace
 
 extern "C" int zmi_apply_delay_pattern(const int64_t* codes, int64_t* out, int batch, int T, int64_t mask_token,
@@ -664,7 +710,7 @@ extern "C" int zmi_sample_logits(const float* logits, const int* generated, int 
   a.gen = generated;
   a.gen_len = generated ? gen_len : 0;
   a.params1 = params;
-  hipLaunchKernelGGL(sample_kernel, dim3(ZMI_NCB, batch), dim3(SORT_THREADS), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(sample_kernel<2>, dim3(ZMI_NCB, batch), dim3(SORT_THREADS), 0, (hipStream_t)stream, a);
   ZMI_CHECK(hipGetLastError());
   return 0;
 }
@@ -676,6 +722,8 @@ extern "C" int zmi_sample_step(const ZmiSlots* slots, const float* logits_rows, 
   if (slot_begin < 0 || slot_begin + slot_count > slots->n_slots) return zmi_fail_msg("sample: slot range");
   if (emb && (d % 8 || !x)) return zmi_fail_msg("sample: fused embedding needs x and d % 8 == 0");
   if (!row_kv != !row_pos) return zmi_fail_msg("sample: row_kv and row_pos go together");
+  const int rps = slots_layout(slots);
+  if (rps < 0) return zmi_fail_msg("sample: rows_per_slot must be 0 or 2 (paired) or 1 (single)");
   SampleArgs a;
   a.sl = *slots;
   a.logits = logits_rows;
@@ -689,7 +737,10 @@ extern "C" int zmi_sample_step(const ZmiSlots* slots, const float* logits_rows, 
   a.x = (bf16_t*)x;
   a.row_kv = row_kv;
   a.row_pos = row_pos;
-  hipLaunchKernelGGL(sample_kernel, dim3(ZMI_NCB, slot_count), dim3(SORT_THREADS), 0, (hipStream_t)stream, a);
+  if (rps == 2)
+    hipLaunchKernelGGL(sample_kernel<2>, dim3(ZMI_NCB, slot_count), dim3(SORT_THREADS), 0, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL(sample_kernel<1>, dim3(ZMI_NCB, slot_count), dim3(SORT_THREADS), 0, (hipStream_t)stream, a);
   ZMI_CHECK(hipGetLastError());
   return 0;
 }
@@ -701,6 +752,8 @@ extern "C" int zmi_sample_step_greedy(const ZmiSlots* slots, const float* logits
     return zmi_fail_msg("sample_greedy: slot range");
   if (emb && (d % 8 || !x)) return zmi_fail_msg("sample_greedy: fused embedding needs x and d % 8 == 0");
   if (!row_kv != !row_pos) return zmi_fail_msg("sample_greedy: row_kv and row_pos go together");
+  const int rps = slots_layout(slots);
+  if (rps < 0) return zmi_fail_msg("sample_greedy: rows_per_slot must be 0 or 2 (paired) or 1 (single)");
   if (slot_count == 0) return 0;
   SampleArgs a{};
   a.sl = *slots;
@@ -713,7 +766,10 @@ extern "C" int zmi_sample_step_greedy(const ZmiSlots* slots, const float* logits
   a.x = (bf16_t*)x;
   a.row_kv = row_kv;
   a.row_pos = row_pos;
-  hipLaunchKernelGGL(sample_greedy_kernel, dim3(slot_count), dim3(64 * ZMI_NCB), 0, (hipStream_t)stream, a);
+  if (rps == 2)
+    hipLaunchKernelGGL(sample_greedy_kernel<2>, dim3(slot_count), dim3(64 * ZMI_NCB), 0, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL(sample_greedy_kernel<1>, dim3(slot_count), dim3(64 * ZMI_NCB), 0, (hipStream_t)stream, a);
   ZMI_CHECK(hipGetLastError());
   return 0;
 }
@@ -721,8 +777,14 @@ extern "C" int zmi_sample_step_greedy(const ZmiSlots* slots, const float* logits
 extern "C" int zmi_embed_step(const ZmiSlots* slots, const void* emb, int d, void* x, int* row_kv, int* row_pos,
                               void* stream) {
   if (d % 8) return zmi_fail_msg("embed: d % 8");
-  hipLaunchKernelGGL(embed_step_kernel, dim3(slots->n_slots), dim3(256), 0, (hipStream_t)stream, *slots,
-                     (const bf16_t*)emb, d, (bf16_t*)x, row_kv, row_pos);
+  const int rps = slots_layout(slots);
+  if (rps < 0) return zmi_fail_msg("embed: rows_per_slot must be 0 or 2 (paired) or 1 (single)");
+  if (rps == 2)
+    hipLaunchKernelGGL(embed_step_kernel<2>, dim3(slots->n_slots), dim3(256), 0, (hipStream_t)stream, *slots,
+                       (const bf16_t*)emb, d, (bf16_t*)x, row_kv, row_pos);
+  else
+    hipLaunchKernelGGL(embed_step_kernel<1>, dim3(slots->n_slots), dim3(256), 0, (hipStream_t)stream, *slots,
+                       (const bf16_t*)emb, d, (bf16_t*)x, row_kv, row_pos);
   ZMI_CHECK(hipGetLastError());
   return 0;
 }

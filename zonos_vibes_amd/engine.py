@@ -10,6 +10,11 @@ the host several times per step).
 Batch layout: utterance slot s owns activation / KV rows 2s (conditional) and 2s+1
 (unconditional), i.e. the reference's `hidden_states.repeat(2, 1, 1)` CFG pair
 (model.py:142) interleaved per slot. Each slot runs the reference's batch_size=1 semantics.
+
+That is the paired layout (rows_per_slot 2), what every cfg_scale but 1 runs. The single layout (rows_per_slot 1,
+set_layout) is the reference's cfg_scale == 1 (model.py:112, 134-136, 193: no repeat, no CFG arithmetic): slot s
+owns activation / KV row s alone, on rows 0 .. S-1 of the same buffers, so a step of k slots runs k rows instead
+of 2k. The layout is a property of a run: it changes only while no slot is active.
 """
 from __future__ import annotations
 
@@ -124,6 +129,7 @@ class HipEngine:
             raise ValueError("the HIP attention kernels are built for head_dim 128")
         self.S = int(max_slots)
         self.R = 2 * self.S
+        self.rps = 2  # rows per slot: 2 = paired (cond, uncond), 1 = single (guidance-free); set_layout()
         self.smax = min(_round8(int(max_seqlen)), ROPE_TABLE_LEN)
         self.tcap = self.smax  # delayed frames per slot never exceed KV positions
         self.max_prefill = int(max_prefill)
@@ -214,7 +220,10 @@ class HipEngine:
         self.batch_shrink = True
         self.slot_greedy = [False] * self.S
         self._plans: dict[tuple, list] = {}
-        self._graphs: dict[tuple, int] = {}
+        # captured decode graphs, one cache per row layout (the sampler launch inside a graph holds the layout):
+        # _graphs is the current layout's, keyed (rows, form, greedy, steps)
+        self._graph_cache: dict[int, dict[tuple, int]] = {2: {}, 1: {}}
+        self._graphs = self._graph_cache[2]
         # host-side upper bound of each slot's next decode position (prefill sets it, every step adds 1):
         # it picks the attention form of a run of steps without reading the device
         self.pos_hi = [0] * self.S
@@ -409,9 +418,10 @@ class HipEngine:
 
     def _build_plan(self):
         """Invalidate the per-row-count decode plans and graphs (new weights or buffers)."""
-        for g in self._graphs.values():
-            _lib.check(self.lib.zmi_graph_destroy(g))
-        self._graphs.clear()
+        for graphs in self._graph_cache.values():
+            for g in graphs.values():
+                _lib.check(self.lib.zmi_graph_destroy(g))
+            graphs.clear()
         self._plans.clear()
 
     def _block_slices(self, form: str) -> int:
@@ -439,7 +449,7 @@ class HipEngine:
     def _segments(self, n: int, slots: int) -> list:
         """Split a run of n decode steps of slots 0..slots-1 into (steps, form) pieces: each piece's
         positions (host bound pos_hi .. + steps - 1) stay within its form's reach."""
-        rows = 2 * slots
+        rows = self.rps * slots
         p0 = max(self.pos_hi[:slots])
         segs = []
         while n > 0:
@@ -456,9 +466,9 @@ class HipEngine:
         return segs
 
     def _plan(self, rows: int, form: str = "none") -> list:
-        """Decode-step launches for the first `rows` rows (slots 0 .. rows/2 - 1). Every kernel's
+        """Decode-step launches for the first `rows` rows (slots 0 .. rows / rows_per_slot - 1). Every kernel's
         per-row arithmetic is independent of `rows` and of the launch form, so a slot decodes
-        identically in any plan."""
+        identically in any plan; the launches depend on the row count alone, so both layouts share them."""
         if (rows, form) not in self._plans:
             w, d, qd = self.w, self.d, self.H * self.hd
             qkv_n = (self.H + 2 * self.Hkv) * self.hd
@@ -616,7 +626,33 @@ class HipEngine:
         s = self.S if slots is None else int(slots)
         if not 1 <= s <= self.S:
             raise ValueError(f"slots {s} outside 1..{self.S}")
-        return 2 * s
+        return self.rps * s
+
+    def set_layout(self, rows_per_slot: int):
+        """The row layout of the runs that follow: 2 = paired (slot s on rows 2s, 2s + 1: guidance), 1 = single (slot
+        s on row s: the reference's cfg_scale == 1). Only while no slot is active. A change leaves nothing of the
+        other layout behind: every row inactive, every hand-off granule zeroed, the slots' state cleared; the
+        captured graphs are cached per layout (_graph_cache), and the KV / Mamba2 state of a row is rewritten by the
+        prefill of the slot that next owns it."""
+        if rows_per_slot not in (1, 2):
+            raise ValueError(f"rows_per_slot must be 1 (single) or 2 (paired), got {rows_per_slot!r}")
+        if rows_per_slot == self.rps:
+            return
+        self.stream.synchronize()
+        if bool(self.st["active"].any().item()):
+            raise RuntimeError("set_layout: a slot is active (the layout is a property of a run)")
+        self.pos_hi = [0] * self.S
+        self.rps = rows_per_slot
+        self.slots.rows_per_slot = rows_per_slot
+        self._graphs = self._graph_cache[rows_per_slot]
+        with torch.cuda.stream(self.stream):
+            self.row_pos.fill_(-1)
+            self.row_kv.zero_()
+            self.st_all.zero_()
+            self._reset_all_granules()
+
+    def _reset_all_granules(self):
+        self.blk_gran.zero_()
 
     def enqueue_step(self, noise: torch.Tensor | None = None, slots: int | None = None, form: str | None = None):
         """One decode step for slots 0 .. slots-1 (default: all; reference model.py:276-307), enqueued
@@ -625,8 +661,8 @@ class HipEngine:
         form: the attention form (default: from the slots' position bounds; the bound advances)."""
         rows = self._rows(slots)
         if form is None:
-            form = self._segments(1, rows // 2)[0][1]
-            self._advance(1, rows // 2)
+            form = self._segments(1, rows // self.rps)[0][1]
+            self._advance(1, rows // self.rps)
         for kind, item in self._plan(rows, form):
             if kind == "gemv":
                 self._run_gemv(item)
@@ -643,16 +679,17 @@ class HipEngine:
                 self._attention(i, self.q, rows, None, self.row_pos, self.smax - 1, self.attn, pf)
             else:  # "call": a prepared launch (hybrid kernels)
                 item()
-        self._sample(self.logits, noise, 0, 0, rows // 2)
+        self._sample(self.logits, noise, 0, 0, rows // self.rps)
 
     def capture(self, slots: int | None = None, form: str = "none", steps: int = 1):
         """The hipGraph of `steps` consecutive decode steps of slots 0 .. slots-1 in one attention form (the loop
         state lives on the device, so a graph of several steps is the one-step graph's launches repeated)."""
         rows = self._rows(slots)
-        key = (rows, form, self._greedy_step(0, rows // 2), steps)
+        slots = rows // self.rps
+        key = (rows, form, self._greedy_step(0, slots), steps)  # in the current layout's cache (set_layout)
         if key not in self._graphs:
             self._graphs[key] = _lib.capture(
-                self.sptr, lambda: [self.enqueue_step(slots=rows // 2, form=form) for _ in range(steps)])
+                self.sptr, lambda: [self.enqueue_step(slots=slots, form=form) for _ in range(steps)])
         return self._graphs[key]
 
     def _advance(self, n: int, slots: int):
@@ -664,7 +701,7 @@ class HipEngine:
         form: a run switches form where the slots' position bound crosses a form's reach)."""
         if n <= 0:
             return
-        s = self._rows(slots) // 2
+        s = self._rows(slots) // self.rps
         for k, form in self._segments(n, s):
             if use_graph:
                 # multi-step graphs only for small batches: the many-slot share (C3) captures a graph per busy-slot
@@ -690,14 +727,19 @@ class HipEngine:
             raise ValueError(f"prefill length {s_len} > engine max_prefill {self.max_prefill}")
         if s_len + max_new_tokens + 8 > self.smax or p + max_new_tokens + 9 > self.tcap:
             raise ValueError("utterance longer than the engine's KV capacity")
-        if cond.shape[0] != 2 or cond.shape[2] != self.d:
+        if self.rps == 1:  # [2, Lc, d] as prepare_conditioning hands it out: row 0 (the conditional one) is used
+            if cond.shape[0] not in (1, 2) or cond.shape[2] != self.d:
+                raise ValueError("prefix_conditioning must be [1, Lc, d_model] (or [2, Lc, d_model]: row 0 is used) "
+                                 "in the single layout")
+        elif cond.shape[0] != 2 or cond.shape[2] != self.d:
             raise ValueError("prefix_conditioning must be [2 (cond, uncond), Lc, d_model]")
         return s_len
 
     def _prefill_stage(self, slot: int, cond: torch.Tensor, prefix: torch.Tensor | None, max_new_tokens: int,
                        params: SamplingParams, off: int, s_len: int):
         """The slot's sampling parameters, delayed-code buffer and granules, and its 2 x s_len prefill rows
-        (cond, uncond) at row `off` of the prefill buffers (reference model.py:181-196, 240-250)."""
+        (cond, uncond) at row `off` of the prefill buffers (reference model.py:181-196, 240-250); in the single
+        layout its one sequence of s_len rows, into KV row `slot`."""
         assert 0 <= slot < self.S
         L, d = self.lib, self.d
         lc = cond.shape[1]
@@ -713,17 +755,16 @@ class HipEngine:
         self.slot_greedy[slot] = params.temperature <= 0
         _lib.check(L.zmi_delay_init(ctypes.byref(self.slots), slot, pr.data_ptr(), p, total, self.sptr), "delay")
         self._reset_granules(slot)  # no granule of an earlier utterance may match a tag
-        xp = self.x_pre[off: off + 2 * s_len]
-        xp[:lc] = cond[0]
-        xp[s_len: s_len + lc] = cond[1]
+        rps = self.rps
+        xp = self.x_pre[off: off + rps * s_len]
         codes = self.delayed[slot]
-        for half in range(2):
+        ar = torch.arange(s_len, dtype=torch.int32, device=self.dev)
+        for half in range(rps):
+            xp[half * s_len: half * s_len + lc] = cond[half]
             _lib.check(L.zmi_embed_codes(codes.data_ptr(), self.tcap, p + 1, self.w["emb"].data_ptr(), d,
                                          xp[half * s_len + lc].data_ptr(), d, self.sptr), "embed_codes")
-        ar = torch.arange(s_len, dtype=torch.int32, device=self.dev)
-        self.row_pos_pre[off: off + 2 * s_len] = torch.cat([ar, ar])
-        self.row_kv_pre[off: off + s_len] = 2 * slot
-        self.row_kv_pre[off + s_len: off + 2 * s_len] = 2 * slot + 1
+            self.row_pos_pre[off + half * s_len: off + (half + 1) * s_len] = ar
+            self.row_kv_pre[off + half * s_len: off + (half + 1) * s_len] = rps * slot + half
 
     def _prefill_finish(self, slot: int, max_new_tokens: int, off: int, s_len: int, p: int, noise):
         """Heads of the slot's last prefill rows, slot state, first sample + frame write (model.py:251-264)."""
@@ -743,13 +784,14 @@ class HipEngine:
         self.stream.wait_stream(torch.cuda.current_stream(self.dev))
         with torch.cuda.stream(self.stream):
             self._prefill_stage(slot, cond, prefix, max_new_tokens, params, 0, s_len)
-            self._prefill_layers(2 * s_len, s_len - 1, self._slot_seqs(slot, 0, s_len))
+            self._prefill_layers(self.rps * s_len, s_len - 1, self._slot_seqs(slot, 0, s_len, self.rps))
             self._prefill_finish(slot, max_new_tokens, 0, s_len, p, noise)
         return s_len
 
     def prefill_many(self, items) -> list:
         """prefill() of several slots: items are (slot, cond, prefix, max_new_tokens, params). Their rows are
-        packed into passes of up to `pre_rows` rows, each pass through the layers once (one weight stream for
+        packed (rows_per_slot x s_len each, so the single layout admits twice as many utterances to a pass)
+        into passes of up to `pre_rows` rows, each pass through the layers once (one weight stream for
         all of them). Every kernel's per-row arithmetic is independent of the rows beside it (the GEMV / GEMM /
         split-K forms and the attention are tested batch-invariant), so each slot decodes exactly as if it had
         been prefilled alone (generate_batch == generate)."""
@@ -759,36 +801,37 @@ class HipEngine:
         lens = [self._prefill_check(it[1], it[2], it[3]) for it in items]
         groups, cur, rows = [], [], 0
         for it, s_len in zip(items, lens):
-            if cur and rows + 2 * s_len > self.pre_rows:
+            if cur and rows + self.rps * s_len > self.pre_rows:
                 groups.append(cur)
                 cur, rows = [], 0
             cur.append((it, s_len, rows))
-            rows += 2 * s_len
+            rows += self.rps * s_len
         groups.append(cur)
         self.stream.wait_stream(torch.cuda.current_stream(self.dev))
         with torch.cuda.stream(self.stream):
             for g in groups:
                 for (slot, cond, prefix, mnt, params), s_len, off in g:
                     self._prefill_stage(slot, cond, prefix, mnt, params, off, s_len)
-                m = g[-1][2] + 2 * g[-1][1]
-                self._prefill_layers(m, max(s_len for _, s_len, _ in g) - 1,
-                                     [sq for it, s_len, off in g for sq in self._slot_seqs(it[0], off, s_len)])
+                m = g[-1][2] + self.rps * g[-1][1]
+                seqs = [sq for it, s_len, off in g for sq in self._slot_seqs(it[0], off, s_len, self.rps)]
+                self._prefill_layers(m, max(s_len for _, s_len, _ in g) - 1, seqs)
                 for (slot, cond, prefix, mnt, params), s_len, off in g:
                     self._prefill_finish(slot, mnt, off, s_len, s_len - cond.shape[1] - 1, None)
         return lens
 
     def _reset_granules(self, slot: int):
         """Zero the in-launch hand-off granules of the slot's rows (tags are positions + 1)."""
-        if 2 * slot < self.blk_rows:
-            self.blk_gran[:, 2 * slot: 2 * slot + 2].zero_()
+        r0 = self.rps * slot
+        if r0 < self.blk_rows:
+            self.blk_gran[:, r0: r0 + self.rps].zero_()
 
     def _prefill_logits(self, s_len: int, off: int = 0):
         """Heads of the last position of the cond / uncond prefill rows (starting at row `off`) -> logits_pre
         (model.py:103-116)."""
         xp = self.x_pre
-        self.x_last[0] = xp[off + s_len - 1]
-        self.x_last[1] = xp[off + 2 * s_len - 1]
-        self._run_gemv(self._gemv(self.w["heads"], self.x_last, 2, HEADS_N_PAD, self.d, _lib.EPI_LOGITS,
+        for half in range(self.rps):  # (single layout: the one sequence's last row)
+            self.x_last[half] = xp[off + (half + 1) * s_len - 1]
+        self._run_gemv(self._gemv(self.w["heads"], self.x_last, self.rps, HEADS_N_PAD, self.d, _lib.EPI_LOGITS,
                                   self.logits_pre, 0, n_valid=HEADS_N, ln=(self.w["nf_w"], self.w["nf_b"])))
 
     def final_norm_pre(self, m: int, out: torch.Tensor):
@@ -804,10 +847,11 @@ class HipEngine:
                                                ln[1].data_ptr(), self.eps, out.data_ptr(), self.d, self.sptr), "ln")
 
     @staticmethod
-    def _slot_seqs(slot: int, off: int, s_len: int) -> list:
+    def _slot_seqs(slot: int, off: int, s_len: int, rps: int = 2) -> list:
         """The slot's two prefill sequences (cond, uncond) as ZmiAttnSeq rows (q_row0, len, kv_row, pos0): s_len rows
-        each from row `off` of the prefill buffers, KV rows 2 slot and 2 slot + 1, from position 0."""
-        return [(off, s_len, 2 * slot, 0), (off + s_len, s_len, 2 * slot + 1, 0)]
+        each from row `off` of the prefill buffers, KV rows 2 slot and 2 slot + 1, from position 0. Single layout
+        (rps 1): its one sequence, KV row slot."""
+        return [(off + half * s_len, s_len, rps * slot + half, 0) for half in range(rps)]
 
     def _prefill_table(self, seqs):
         """The device and host tables of zmi_attention_prefill for one pass (None under prefill_attn = "rows"):
@@ -914,7 +958,7 @@ class HipEngine:
         self.pos_hi[slot] = 0
         with torch.cuda.stream(self.stream):
             self.st["active"][slot] = 0
-            self.row_pos[2 * slot: 2 * slot + 2] = -1
+            self.row_pos[self.rps * slot: self.rps * (slot + 1)] = -1
 
 
 def check_weights(weights: str, hybrid: bool) -> None:

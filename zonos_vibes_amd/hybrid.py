@@ -182,7 +182,11 @@ class HybridEngine(HipEngine):
 
     def _reset_granules(self, slot: int):
         super()._reset_granules(slot)
-        self.mgran[:, 2 * slot: 2 * slot + 2].zero_()
+        self.mgran[:, self.rps * slot: self.rps * (slot + 1)].zero_()
+
+    def _reset_all_granules(self):
+        super()._reset_all_granules()
+        self.mgran.zero_()
 
     # ------------------------------------------------------------------ launch helpers
     def _addln(self, hid, res, ln, out, m, store=True):
@@ -389,15 +393,16 @@ class HybridEngine(HipEngine):
                     item()
 
     def _prefill_logits(self, s_len: int, off: int = 0):
-        """norm_f + heads of the last position of the cond / uncond sequences that start at row `off`."""
+        """norm_f + heads of the last position of the cond / uncond sequences that start at row `off` (single layout:
+        of the one sequence)."""
         d = self.d
         byte = (off + s_len - 1) * d * 2  # row off + s_len - 1, then the uncond row s_len further on
         lib = self.lib
         _lib.check(lib.zmi_add_layernorm(self.hid_pre.data_ptr() + byte, s_len * d, self.x_pre.data_ptr() + byte,
-                                         s_len * d, 2, d, self.w["nf_w"].data_ptr(), self.w["nf_b"].data_ptr(),
+                                         s_len * d, self.rps, d, self.w["nf_w"].data_ptr(), self.w["nf_b"].data_ptr(),
                                          self.eps, self.x_last.data_ptr(), d, 0, self.sptr), "norm_f")
-        self._run_gemv(self._gemv(self.w["heads"], self.x_last, 2, HEADS_N_PAD, d, _lib.EPI_LOGITS, self.logits_pre,
-                                  0, n_valid=HEADS_N))
+        self._run_gemv(self._gemv(self.w["heads"], self.x_last, self.rps, HEADS_N_PAD, d, _lib.EPI_LOGITS,
+                                  self.logits_pre, 0, n_valid=HEADS_N))
 
     def final_norm_pre(self, m: int, out: torch.Tensor):
         _lib.check(self.lib.zmi_add_layernorm(self.hid_pre.data_ptr(), self.d, self.x_pre.data_ptr(), self.d, m,

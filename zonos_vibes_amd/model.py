@@ -6,10 +6,15 @@
     for wav in model.stream(prefix_conditioning): ...                    # the same samples, in chunks, as they are ready
     for i, wav, last in model.stream_batch(conds): ...                   # many utterances' chunks, each as decode(generate_batch)
     with model.serve(64, 2048, 512, pcm16=True) as session: ...          # requests admitted mid-stream (serving.py)
+    codes = model.generate(prefix_conditioning[:1], cfg_scale=1)         # guidance-free: one row per utterance
 
 `generate` keeps the reference's arguments and batch_size=1 semantics; `generate_batch`
 runs many independent utterances through the slots of one engine (continuous batching at
 chunk granularity), each with exactly the per-utterance result of `generate`.
+
+cfg_scale == 1 is the reference's guidance-free branch (zonos/model.py:112, 134-136, 193): no unconditional row is
+run at all. Such a call runs the engine's single layout (one activation / KV row per utterance, engine.set_layout);
+any other cfg_scale runs the paired layout. The layout is chosen per call, so one model serves both.
 """
 from __future__ import annotations
 
@@ -112,6 +117,18 @@ class Zonos:
             self.engine.w = w
             self.engine._build_plan()
 
+    def _select_layout(self, cfg_scale: float) -> int:
+        """The engine's row layout for a call (after _ensure_capacity, which may have rebuilt the engine): single
+        (one row per utterance) for cfg_scale == 1, the reference's guidance-free branch, else paired."""
+        rps = 1 if cfg_scale == 1 else 2
+        self.engine.set_layout(rps)
+        return rps
+
+    @staticmethod
+    def _cond_rows_ok(cond: torch.Tensor, cfg_scale: float) -> bool:
+        """[2, Lc, d] (cond, uncond); with cfg_scale == 1 also [1, Lc, d] (of [2, Lc, d] row 0 alone is used)."""
+        return cond.shape[0] == 2 or (cfg_scale == 1 and cond.shape[0] == 1)
+
     # ------------------------------------------------------------------ speaker embedding
     def load_speaker_model(self, ckpt_path: str, lda_path: str) -> None:
         """The published speaker encoder and its LDA (speaker_cloning.py:391-406) from local .pt / .safetensors
@@ -160,15 +177,17 @@ class Zonos:
                  callback: Callable[[torch.Tensor, int, int], bool] | None = None,
                  chunk: int = 64) -> torch.Tensor:
         """Reference model.py:218-315 (batch_size=1). `disable_torch_compile` is accepted and ignored:
-        the decode step is a hipGraph of hand-written kernels in every mode."""
-        assert cfg_scale != 1, "TODO: add support for cfg_scale=1"
+        the decode step is a hipGraph of hand-written kernels in every mode. cfg_scale == 1: the guidance-free
+        branch (model.py:112), one row through the backbone; prefix_conditioning [1, Lc, d], or [2, Lc, d] of which
+        row 0 is used."""
         self._check_not_serving("generate")
-        if batch_size != 1 or prefix_conditioning.shape[0] != 2:
+        if batch_size != 1 or not self._cond_rows_ok(prefix_conditioning, cfg_scale):
             raise ValueError("the reference generate() supports batch_size=1 only (SURVEY.md §0.3); "
                              "use generate_batch() for many utterances")
         lc = prefix_conditioning.shape[1]
         p = 0 if audio_prefix_codes is None else audio_prefix_codes.shape[2]
         self._ensure_capacity(1, lc + p + max_new_tokens + 9, lc + p + 1)
+        self._select_layout(cfg_scale)
         e = self.engine
         params = SamplingParams.from_dict(dict(sampling_params), cfg_scale, _draw_seed())
         slot = 0
@@ -228,18 +247,21 @@ class Zonos:
 
         decoder: "window" (the default) or "carry", the carried-state DAC decoder (autoencoder.stream_decoder(carry=
         True)): the same chunks, each decoded at the cost of its own frames; a round's rollback point then holds a
-        copy of the decoder's state."""
-        assert cfg_scale != 1, "TODO: add support for cfg_scale=1"
+        copy of the decoder's state.
+
+        cfg_scale == 1: guidance-free, as generate(cfg_scale=1)."""
         self._check_not_serving("stream")
         carry = self._decoder_mode(decoder)
         rate = self._output_rate(sample_rate)
-        if prefix_conditioning.shape[0] != 2:
-            raise ValueError("stream() has generate()'s batch_size=1 semantics: prefix_conditioning [2, Lc, d]")
+        if not self._cond_rows_ok(prefix_conditioning, cfg_scale):
+            raise ValueError("stream() has generate()'s batch_size=1 semantics: prefix_conditioning [2, Lc, d] "
+                             "([1, Lc, d] too with cfg_scale=1)")
         if chunk_frames < 1:
             raise ValueError("chunk_frames >= 1")
         lc = prefix_conditioning.shape[1]
         p = 0 if audio_prefix_codes is None else audio_prefix_codes.shape[2]
         self._ensure_capacity(1, lc + p + max_new_tokens + 9, lc + p + 1)
+        self._select_layout(cfg_scale)
         e = self.engine
         params = SamplingParams.from_dict(dict(sampling_params), cfg_scale, _draw_seed())
         slot = 0
@@ -333,7 +355,8 @@ class Zonos:
                        max_new_tokens: Sequence[int] | int = 86 * 30, cfg_scale: float = 2.0,
                        sampling_params: dict = dict(min_p=0.1), seeds: Sequence[int] | None = None,
                        max_slots: int | None = None, chunk: int = 32) -> list[torch.Tensor]:
-        """Many independent utterances through the engine's slots; result i equals generate() on utterance i."""
+        """Many independent utterances through the engine's slots; result i equals generate() on utterance i.
+        cfg_scale == 1: guidance-free (one row per utterance, so a step of k busy slots runs k rows, not 2 k)."""
         self._check_not_serving("generate_batch")
         n = len(conds)
         prefixes = list(prefixes) if prefixes is not None else [None] * n
@@ -343,6 +366,7 @@ class Zonos:
         need_pre = max(c.shape[1] + (0 if p is None else p.shape[2]) + 1 for c, p in zip(conds, prefixes))
         slots = min(max_slots or n, n)
         self._ensure_capacity(slots, need_seq, need_pre)
+        self._select_layout(cfg_scale)
         e = self.engine
         # longest-processing-time first, so the tail is short
         order = sorted(range(n), key=lambda i: -mnt[i])
@@ -400,8 +424,8 @@ class Zonos:
         A round is `chunk_frames` decode steps over slots 0 .. the highest busy one (generate_batch's sizes and
         batch_shrink rule), one copy of every slot's state to the host, the read of the frames the round made final
         in every busy slot, and ONE push of all of them to a DACBatchStreamDecoder, which decodes the slots' windows
-        of equal shape as lanes of one launch sequence. Slots that ended are flushed and refilled from the queue
-        (longest first). The DAC windows run between the rounds, never beside decode steps (stream()'s ordering rule,
+        of equal shape as lanes of one launch sequence (cfg_scale == 1: guidance-free, one row per slot). Slots that
+        ended are flushed and refilled from the queue (longest first). The DAC windows run between the rounds, never beside decode steps (stream()'s ordering rule,
         DESIGN.md §5g): they are ordered behind the round's reads and the next round's steps wait for the
         autoencoder's stream. The state is read before the push, so nothing is decoded past an utterance's end.
 
@@ -412,7 +436,6 @@ class Zonos:
         decoder: "window" (the default) or "carry", the carried-state DAC decoder (autoencoder.stream_decoder_batch(
         carry=True)): the same items; the slots that push equal frame counts past their start are one launch sequence
         whatever their positions, and a round decodes the frames it made final, not their windows."""
-        assert cfg_scale != 1, "TODO: add support for cfg_scale=1"
         self._check_not_serving("stream_batch")
         carry = self._decoder_mode(decoder)
         rate = self._output_rate(sample_rate)
@@ -429,6 +452,7 @@ class Zonos:
         need_pre = max(c.shape[1] + p + 1 for c, p in zip(conds, plen))
         slots = min(max_slots or n, n)
         self._ensure_capacity(slots, need_seq, need_pre)
+        self._select_layout(cfg_scale)
         e, ae = self.engine, self.autoencoder
         key = (id(ae), int(chunk_frames), carry)
         dec = self._stream_batch_decoders.get(key)
@@ -472,16 +496,21 @@ class Zonos:
                     e.release(s)
 
     def serve(self, max_slots: int, max_seqlen: int, max_prefill: int, chunk_frames: int = 16,
-              pcm16: bool = False, sample_rate: int | None = None, decoder: str = "window") -> ServeSession:
+              pcm16: bool = False, sample_rate: int | None = None, decoder: str = "window",
+              guidance: bool = True) -> ServeSession:
         """A serving session (serving.ServeSession, a context manager): submit() requests from any thread while
         others are being spoken, run_round() from one thread hands out every ticket's chunks, each ticket's
         concatenated bit for bit decode(generate_batch()) of the request alone; with pcm16 they leave as int16 CPU
         tensors (zmi_pcm16_pack); with sample_rate they leave at that rate (zmi_resample between the round's waveforms
         and the egress; None or 44100: no resampler, the unchanged path); decoder "window" or "carry" as in
         stream_batch(). Capacity is fixed here; while the session is
-        open generate(), stream(), generate_batch(), stream_batch() and another serve() raise RuntimeError."""
+        open generate(), stream(), generate_batch(), stream_batch() and another serve() raise RuntimeError.
+        guidance=False opens a guidance-free session (the single layout, one row per slot): its submit() takes
+        cfg_scale=1 only, and conditioning [1, Lc, d] or [2, Lc, d]. A session is one or the other; guided and
+        guidance-free requests do not mix in one session."""
         self._check_not_serving("serve")
-        return ServeSession(self, max_slots, max_seqlen, max_prefill, chunk_frames, pcm16, sample_rate, decoder)
+        return ServeSession(self, max_slots, max_seqlen, max_prefill, chunk_frames, pcm16, sample_rate, decoder,
+                            guidance)
 
     @staticmethod
     def _decoder_mode(decoder: str) -> bool:

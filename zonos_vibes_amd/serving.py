@@ -42,11 +42,13 @@ class SlotScheduler:
     submit() / cancel() / wait_for_work() may be called from any thread; begin_round() / finish() / release_all() from
     the one thread that drives the engine."""
 
-    def __init__(self, max_slots: int, max_seqlen: int, max_prefill: int, d_model: int | None = None):
+    def __init__(self, max_slots: int, max_seqlen: int, max_prefill: int, d_model: int | None = None,
+                 guidance: bool = True):
         if max_slots < 1:
             raise ValueError("max_slots >= 1")
         self.max_slots, self.max_seqlen, self.max_prefill = int(max_slots), int(max_seqlen), int(max_prefill)
         self.d_model = d_model
+        self.guidance = bool(guidance)  # False: a guidance-free session, conditioning [1, Lc, d] too
         self._cond = threading.Condition()
         self._next = 0
         self._waiting: deque = deque()
@@ -57,8 +59,10 @@ class SlotScheduler:
     def fit(self, cond_shape, prefix_shape, max_new_tokens: int) -> tuple:
         """(Lc, P) of a request that fits a slot; ValueError for one that never can."""
         cond_shape = tuple(cond_shape)
-        if len(cond_shape) != 3 or cond_shape[0] != 2 or (self.d_model is not None and cond_shape[2] != self.d_model):
-            raise ValueError(f"prefix_conditioning must be [2 (cond, uncond), Lc, d_model], got {list(cond_shape)}")
+        rows_ok = len(cond_shape) == 3 and (cond_shape[0] == 2 or (cond_shape[0] == 1 and not self.guidance))
+        if not rows_ok or (self.d_model is not None and cond_shape[2] != self.d_model):
+            want = "[2 (cond, uncond), Lc, d_model]" if self.guidance else "[1, Lc, d_model] or [2, Lc, d_model]"
+            raise ValueError(f"prefix_conditioning must be {want}, got {list(cond_shape)}")
         p = 0
         if prefix_shape is not None:
             prefix_shape = tuple(prefix_shape)
@@ -320,10 +324,13 @@ class ServeSession:
     seeds=[seed])[0]) (with sample_rate, autoencoder.resample(that, 44100, sample_rate); with pcm16, the waveform's
     clamp(-1, 1) * 32767 truncated to int16, a launch of its own behind the resampler's), whenever the request was
     admitted, whichever slot it got and whatever the other slots were doing: the stepping kernels are row-invariant.
-    Every ticket that is not cancelled gets exactly one item with last = True (its chunk may be empty)."""
+    Every ticket that is not cancelled gets exactly one item with last = True (its chunk may be empty).
+    guidance=False: a guidance-free session (the engine's single layout for as long as it is open); submit() then
+    takes cfg_scale=1 only. Guided and guidance-free requests do not mix in one session."""
 
     def __init__(self, model, max_slots: int, max_seqlen: int, max_prefill: int, chunk_frames: int = 16,
-                 pcm16: bool = False, sample_rate: int | None = None, decoder: str = "window"):
+                 pcm16: bool = False, sample_rate: int | None = None, decoder: str = "window",
+                 guidance: bool = True):
         if chunk_frames < 1:
             raise ValueError("chunk_frames >= 1")
         carry = model._decoder_mode(decoder)
@@ -331,8 +338,10 @@ class ServeSession:
         if getattr(model, "_serving", None) is not None:
             raise RuntimeError("a serve() session is already open on this model")
         self.model, self.pcm16 = model, bool(pcm16)
-        self.sched = SlotScheduler(max_slots, max_seqlen, max_prefill, model.config.backbone.d_model)
+        self.guidance = bool(guidance)
+        self.sched = SlotScheduler(max_slots, max_seqlen, max_prefill, model.config.backbone.d_model, self.guidance)
         model._ensure_capacity(max_slots, max_seqlen, max_prefill)  # once: a session never rebuilds the engine
+        model._select_layout(2.0 if self.guidance else 1)  # the session's layout, for as long as it is open
         e, ae = model.engine, model.autoencoder
         key = (id(ae), int(chunk_frames), carry)
         dec = model._stream_batch_decoders.get(key)
@@ -355,7 +364,10 @@ class ServeSession:
         is untouched)."""
         from .engine import SamplingParams
         from .model import _draw_seed
-        assert cfg_scale != 1, "TODO: add support for cfg_scale=1"
+        if self.guidance:
+            assert cfg_scale != 1, "cfg_scale=1 runs in a serve(guidance=False) session (one layout per session)"
+        elif cfg_scale != 1:
+            raise ValueError(f"a serve(guidance=False) session takes cfg_scale=1 only, got {cfg_scale!r}")
         self.sched.fit(cond.shape, None if audio_prefix_codes is None else audio_prefix_codes.shape, max_new_tokens)
         params = SamplingParams.from_dict(dict(sampling_params), cfg_scale, _draw_seed() if seed is None else seed)
         return self.sched.submit(cond.shape, None if audio_prefix_codes is None else audio_prefix_codes.shape,
