@@ -393,8 +393,11 @@ __global__ __launch_bounds__(256) void mamba2_scan2_kernel(const ZmiMamba2Args a
 //   y = M_hi X + M_lo X    bf16 MFMA (x exactly bf16), fp32 sums, + D x, rounded to bf16;
 //   state = W^T B with W[s][p] = exp(cum[T-1] - cum[s]) dt_s x_s[p] split the same way, rounded to bf16 (the cache dtype).
 // cum is a fixed-shape scan (lane L owns positions 4L .. 4L + 3, lane totals by a shuffle scan) computed identically by
-// every role. Arithmetic differs from the recurrence in fp32 rounding (and the hi / lo split keeps ~16 mantissa bits
-// of M and W): checked against the oracle's recurrence like the scan forms.
+// every role, in fp64, and cum[t] - cum[s] is taken in fp64 before expf: one fp32 running sum over the sequence carries
+// an absolute error of ~ |cum| 2^-23 into every exponent, however small the difference (a head that forgets, A dt ~
+// -480 for a few positions, leaves |cum| in the thousands and every later decay wrong by 2^-11; tests/mamba_cases.py,
+// regime reset). Arithmetic differs from the recurrence in fp32 rounding (and the hi / lo split keeps ~16 mantissa
+// bits of M and W): checked against the fp64 recurrence like the scan forms (tests/test_gpu_mamba_probe.py).
 constexpr int SSD_TB = 32;      // y rows per block of the y workgroup
 constexpr int SSD_NT = 1024;    // threads: 16 waves
 constexpr int SSD_TMAX = 256;   // longest sequence of this form
@@ -406,9 +409,10 @@ constexpr int SSD_XROW = MB_HD + 8;  // x / W row stride (bf16)
 struct SsdLds {
   int S32;  // positions rounded up to 32
   __device__ __host__ SsdLds(int T) : S32((T + 31) / 32 * 32) {}
-  // y role: cum, dt | B rows [S32][SSD_BROW] | C rows [32][SSD_BROW] | M hi / lo [32][S32 + 8] | x rows [S32][SSD_XROW]
+  // y role: cum (fp64), dt | B rows [S32][SSD_BROW] | C rows [32][SSD_BROW] | M hi / lo [32][S32 + 8] | x rows
+  // [S32][SSD_XROW]: 152,064 bytes at T = 256
   __device__ __host__ int MP() const { return S32 + 8; }
-  __device__ __host__ size_t b_off() const { return 2 * SSD_TMAX * 4; }
+  __device__ __host__ size_t b_off() const { return SSD_TMAX * 8 + SSD_TMAX * 4; }
   __device__ __host__ size_t c_off() const { return b_off() + (size_t)S32 * SSD_BROW * 2; }
   __device__ __host__ size_t mh_off() const { return c_off() + (size_t)SSD_TB * SSD_BROW * 2; }
   __device__ __host__ size_t ml_off() const { return mh_off() + (size_t)SSD_TB * MP() * 2; }
@@ -451,8 +455,8 @@ __global__ __launch_bounds__(SSD_NT) void mamba2_ssd_kernel(const ZmiMamba2Args 
   const int row0 = sq.row0, conv_dim = a.d_ssm + 2 * MB_DS;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const SsdLds L(T);
-  float* cum = reinterpret_cast<float*>(smem);
-  float* dtl = cum + SSD_TMAX;
+  double* cum = reinterpret_cast<double*>(smem);
+  float* dtl = reinterpret_cast<float*>(cum + SSD_TMAX);
   const float Ah = a.A[h];
   const bool state_role = role == 1;
   const int s32 = L.S32;
@@ -466,22 +470,22 @@ __global__ __launch_bounds__(SSD_NT) void mamba2_ssd_kernel(const ZmiMamba2Args 
     *reinterpret_cast<uint4*>(Bs + r * SSD_BROW + 8 * c) = v;
   }
   if (wave == 0) {
-    float v[4], run = 0.f;
+    double v[4], run = 0.0;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int q = 4 * lane + i;
       const float d = q < T ? dts[(size_t)(row0 + q) * a.nheads + h] : 0.f;
       dtl[q] = d;
-      run += Ah * d;
+      run += (double)Ah * (double)d;  // the product of two floats: exact
       v[i] = run;
     }
-    float pre = run;  // inclusive scan of the lane totals
+    double pre = run;  // inclusive scan of the lane totals
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
-      const float o = __shfl_up(pre, d, 64);
+      const double o = __shfl_up(pre, d, 64);
       if (lane >= d) pre += o;
     }
-    const float excl = pre - run;
+    const double excl = pre - run;
 #pragma unroll
     for (int i = 0; i < 4; ++i) cum[4 * lane + i] = excl + v[i];
   }
@@ -521,7 +525,11 @@ __global__ __launch_bounds__(SSD_NT) void mamba2_ssd_kernel(const ZmiMamba2Args 
       }
       __syncthreads();  // C block (and, the first time, B / x / cum) visible; the previous block's y reads are done
       if (t0 + SSD_TB < T) load_c(t0 + SSD_TB);
-      // (3) M tiles (16 t x 16 s) over s < 32 sk: G = C B^T on the tiles that reach s <= t, zeros elsewhere
+      // (3) M tiles (16 t x 16 s) over s < 32 sk: G = C B^T on the tiles that reach s <= t, zeros elsewhere. A wave's
+      // tiles share ti = wave & 1 (the stride is even), so its four rows' cum is read once per block
+      double ct[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) ct[i] = cum[t0 + 16 * (wave & 1) + 4 * (lane >> 4) + i];  // < S32 <= SSD_TMAX
       for (int tile = wave; tile < 4 * sk; tile += SSD_NT / 64) {
         const int ti = tile & 1, si = tile >> 1;
         const bool live = 16 * ti < tn && 16 * si <= t0 + 16 * ti + 15;
@@ -534,12 +542,14 @@ __global__ __launch_bounds__(SSD_NT) void mamba2_ssd_kernel(const ZmiMamba2Args 
             g = mfma_bf16(av, bv, g);
           }
         }
-        const int s = 16 * si + (lane & 15);
+        const int s = 16 * si + (lane & 15);  // < 32 sk <= S32
+        const double cs = cum[s];
+        const float ds = dtl[s];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int tl = 16 * ti + 4 * (lane >> 4) + i, tt = t0 + tl;
           float m = 0.f;
-          if (live && tl < tn && s <= tt) m = g[i] * expf(cum[tt] - cum[s]) * dtl[s];
+          if (live && tl < tn && s <= tt) m = g[i] * expf((float)(ct[i] - cs)) * ds;
           uint32_t lo;
           const uint32_t hi = split_bf16(m, &lo);
           Mh[tl * MP + s] = (bf16_t)hi;
@@ -576,14 +586,14 @@ __global__ __launch_bounds__(SSD_NT) void mamba2_ssd_kernel(const ZmiMamba2Args 
     bf16_t* Wh = reinterpret_cast<bf16_t*>(smem + L.wh_off());
     bf16_t* Wl = reinterpret_cast<bf16_t*>(smem + L.wl_off());
     __syncthreads();  // cum / dt
-    const float cT = cum[T - 1];
+    const double cT = cum[T - 1];
     // (2) W rows [s][p] = exp(cum[T-1] - cum[s]) dt_s x_s[p] as hi / lo bf16, zero past T
     for (int i = t; i < s32 * (MB_HD / 8); i += SSD_NT) {
       const int r = i / (MB_HD / 8), c = i % (MB_HD / 8);
       uint32_t hv[4] = {0u, 0u, 0u, 0u}, lv[4] = {0u, 0u, 0u, 0u};
       if (r < T) {
         const uint4 v = *reinterpret_cast<const uint4*>(xc + (size_t)(row0 + r) * conv_dim + h * MB_HD + 8 * c);
-        const float w = expf(cT - cum[r]) * dtl[r];
+        const float w = expf((float)(cT - cum[r])) * dtl[r];
         const uint32_t u[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
