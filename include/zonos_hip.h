@@ -554,6 +554,23 @@ int64_t zmi_mamba2_scan_ws_bytes(int m, int d_ssm, int nheads);
  * live sequences sharing rows or a kv_row, or a small ws are refused (non-zero, zmi_last_error, nothing written). */
 int zmi_mamba2_scan_seqs(const ZmiMamba2Args* args, const ZmiAttnSeq* seqs, int n_seq, const ZmiAttnSeq* seqs_host,
                          void* ws, int64_t ws_bytes, void* stream);
+/* zmi_mamba2_scan_seqs for sequences that may continue: the same table and buffers, pos0 >= 0 per sequence.
+ * pos0 == 0: the sequence starts empty (stale state and ring are not read); y, state and ring are bit for bit those of
+ * zmi_mamba2_scan_seqs. pos0 > 0: it continues from what state row kv_row holds, the bf16 SSM state and the conv ring
+ * (slot q & 3 = raw xBC of position q for q in pos0 - 3 .. pos0 - 1; positions below 0 read as zero whatever their slot
+ * holds), and leaves the final state in the same row and the ring slots of its last min(len, 4) positions (with
+ * len < 4 the other slots keep their bits, as after zmi_mamba2_step). The form is chosen per sequence by len, as in
+ * zmi_mamba2_scan_seqs; the continued SSD form adds y_t += exp(cum[t]) (C_t . h0) (one more bf16 MFMA, fp32 sums) and
+ * state = exp(cum[T-1]) h0 + W^T B, the recurrence forms start their registers from h0. Each sequence's results are bit
+ * for bit those of the call on it alone, whatever its table mates, the table order and the mix of starting and
+ * continuing sequences. Launches: conv + dt (reads the rings, writes none), carry (copies the continued states into ws
+ * and updates the rings), then the scans (the SSD roles read the copies, never the state row the state role writes).
+ * ws: >= zmi_mamba2_scan_cont_ws_bytes(M, d_ssm, nheads, n_cont), n_cont the table's sequences with pos0 > 0 and
+ * len > 0 (one state copy each; starting and empty sequences cost none). Refusals: those of zmi_mamba2_scan_seqs with
+ * "pos0 < 0" (or pos0 + len past INT_MAX) in place of "pos0 != 0", on the host copy, before any launch. */
+int zmi_mamba2_scan_cont(const ZmiMamba2Args* args, const ZmiAttnSeq* seqs, int n_seq, const ZmiAttnSeq* seqs_host,
+                         void* ws, int64_t ws_bytes, void* stream);
+int64_t zmi_mamba2_scan_cont_ws_bytes(int m, int d_ssm, int nheads, int n_cont);
 /* layer_norm_fn(hidden, w, b, residual, prenorm=True): s = hidden + residual (fp32; hidden may be NULL:
  * s = residual), residual <- bf16(s) if store_residual, out = LayerNorm(s) bf16; k in {512 .. 4096}. */
 int zmi_add_layernorm(const void* hidden, int ldh, void* residual, int ldr, int m, int k, const void* w,

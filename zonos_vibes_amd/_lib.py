@@ -214,6 +214,9 @@ _SIGS = {
     "zmi_mamba2_scan_ws_bytes": (ctypes.c_int64, [c_int, c_int, c_int]),
     "zmi_mamba2_scan_seqs": (c_int, [ctypes.POINTER(Mamba2Args), c_void_p, c_int, c_void_p, c_void_p, ctypes.c_int64,
                                      c_void_p]),
+    "zmi_mamba2_scan_cont": (c_int, [ctypes.POINTER(Mamba2Args), c_void_p, c_int, c_void_p, c_void_p, ctypes.c_int64,
+                                     c_void_p]),
+    "zmi_mamba2_scan_cont_ws_bytes": (ctypes.c_int64, [c_int, c_int, c_int, c_int]),
     "zmi_add_layernorm": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_float,
                                   c_void_p, c_int, c_int, c_void_p]),
     "zmi_mamba_block": (c_int, [ctypes.POINTER(GemvArgs), ctypes.POINTER(Mamba2Args), c_void_p, c_void_p, c_void_p]),

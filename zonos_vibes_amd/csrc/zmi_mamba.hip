@@ -141,6 +141,15 @@ __global__ __launch_bounds__(MB_NT) void mamba2_scan_kernel(const ZmiMamba2Args 
 //      256 threads is spread over 1,024 (4x the workgroups, a quarter of each thread's state and FMA chain), and
 //      the conv no longer sits inside it. Its arithmetic differs from mamba2_scan_kernel's in fp32 rounding (fused
 //      multiply-adds, the readout summed over 8-wide blocks): both are checked against the oracle's recurrence.
+// zmi_mamba2_scan_cont (the kernels' CONT instantiations): the same launches for sequences that continue from the state
+// row's bf16 state and conv ring (pos0 > 0 in the table), with mamba2_carry_kernel between (1) and the scans. Three
+// hazards of a continued scan are excluded by construction, each stated at its kernel: (ring) the conv launch only
+// reads rings and the carry launch, next in stream order, only writes them; (state) the SSD roles read h0 from the
+// carry launch's copy in the workspace, never from the state row the state role overwrites, and a recurrence workgroup
+// reads exactly the state rows it alone writes; (LDS) the y role's h0 fragments live in registers, and its C_blk h0^T
+// product is taken between a row block's two barriers, while the C rows in LDS are stable (step (4), which runs while
+// faster waves already refill them, reads none). The plain
+// instantiations (CONT false: zmi_mamba2_scan_ws, zmi_mamba2_scan_seqs) compile to what they were.
 constexpr int S2_NB = MB_DS / 8;        // 16 n-blocks of 8 state columns
 constexpr int S2_TT = 32;               // positions staged per tile
 
@@ -202,6 +211,11 @@ __device__ __forceinline__ int scan_kv(const ZmiMamba2Args& a, const ScanSeqs& q
   return a.row_kv ? a.row_kv[s.row0] : s.idx;
 }
 
+// CONT (zmi_mamba2_scan_cont): a sequence with pos0 > 0 takes the raw inputs of positions pos0 - 3 .. pos0 - 1 from the
+// conv ring of its state row (slot q & 3, zero below position 0), and NO workgroup of this launch writes a ring: the
+// rows 0 .. 2 of a sequence read the ring its last row would overwrite, with no order between them. The ring is
+// updated by mamba2_carry_kernel, the next launch in stream order.
+template <bool CONT>
 __global__ __launch_bounds__(256) void mamba2_conv_kernel(const ZmiMamba2Args a, const ScanSeqs sqs, bf16_t* xc,
                                                           float* dts, float* das) {
   // one thread per (row, channel): grid (rows, channel blocks of 256), every load of the launch in flight at once
@@ -216,13 +230,21 @@ __global__ __launch_bounds__(256) void mamba2_conv_kernel(const ZmiMamba2Args a,
     const bf16_t* cw = reinterpret_cast<const bf16_t*>(a.conv_w);
     const bf16_t* cb = reinterpret_cast<const bf16_t*>(a.conv_b);
     float r[MB_DC];
+    int pos0 = 0;
+    const bf16_t* ring0 = nullptr;  // CONT: the ring the sequence continues from (read only)
+    if constexpr (CONT) {
+      pos0 = sqs.seqs[sq.idx].pos0;
+      ring0 = reinterpret_cast<const bf16_t*>(a.conv_ring) + (size_t)sqs.seqs[sq.idx].kv_row * MB_DC * conv_dim;
+    }
 #pragma unroll
     for (int k = 0; k < MB_DC; ++k) {
       const int qq = q - (MB_DC - 1) + k;
-      r[k] = qq >= 0 ? bf2f(zx0[(size_t)qq * a.ld_zx + c]) : 0.f;
+      if (qq >= 0) r[k] = bf2f(zx0[(size_t)qq * a.ld_zx + c]);
+      else if (CONT && pos0 + qq >= 0) r[k] = bf2f(ring0[(size_t)((pos0 + qq) & 3) * conv_dim + c]);
+      else r[k] = 0.f;
     }
     xc[(size_t)row * conv_dim + c] = (bf16_t)f2bf(conv4(cw + (size_t)c * MB_DC, bf2f(cb[c]), r[0], r[1], r[2], r[3]));
-    if (q == seq_len - 1) {  // the conv ring: slot qq % 4 holds the raw input of qq, for the last d_conv positions
+    if (!CONT && q == seq_len - 1) {  // the conv ring: slot qq % 4 holds the raw input of qq, for the last d_conv positions
       const int kv = scan_kv(a, sqs, sq);
       bf16_t* ring = reinterpret_cast<bf16_t*>(a.conv_ring) + (size_t)kv * MB_DC * conv_dim;
 #pragma unroll
@@ -238,6 +260,48 @@ __global__ __launch_bounds__(256) void mamba2_conv_kernel(const ZmiMamba2Args a,
       dts[(size_t)row * a.nheads + h] = dtv;
       das[(size_t)row * a.nheads + h] = expf(a.A[h] * dtv);
     }
+}
+
+// where the h0 copy of table entry idx sits in the workspace: its rank among the continuing sequences (pos0 > 0, live
+// rows), so starting and empty entries cost no copy
+__device__ __forceinline__ int cont_rank(const ZmiMamba2Args& a, const ScanSeqs& q, int idx) {
+  int r = 0;
+  for (int j = 0; j < idx; ++j) r += (q.seqs[j].pos0 > 0 && scan_rows_ok(q.seqs[j], a.M)) ? 1 : 0;
+  return r;
+}
+
+// zmi_mamba2_scan_cont's second launch, after the conv launch and before the scans, one workgroup per (table entry,
+// head | ring): what a continuing sequence carries, taken out of the other launches' way by stream order alone.
+//   blockIdx.y < nheads   a sequence with pos0 > 0: its head's bf16 state h0 copied to the workspace (h0s, by
+//                         cont_rank). The SSD form's y workgroup reads h0 while its state workgroup overwrites the state
+//                         row, with no order between the two: both read the copy, never the row.
+//   blockIdx.y == nheads  the conv ring: slot (pos0 + q) & 3 <- raw input of the sequence's last min(len, 4) positions
+//                         (the conv launch, the ring's only reader, is complete). pos0 == 0: the slots of positions
+//                         below 0 are zeroed, as zmi_mamba2_scan_seqs leaves them; pos0 > 0: the other slots keep
+//                         their bits, as after zmi_mamba2_step.
+__global__ __launch_bounds__(256) void mamba2_carry_kernel(const ZmiMamba2Args a, const ScanSeqs sqs, bf16_t* h0s) {
+  const ZmiAttnSeq s = sqs.seqs[blockIdx.x];
+  if (!scan_rows_ok(s, a.M)) return;
+  const int conv_dim = a.d_ssm + 2 * MB_DS;
+  if ((int)blockIdx.y == a.nheads) {
+    const bf16_t* zx0 = reinterpret_cast<const bf16_t*>(a.zxbcdt) + (size_t)s.q_row0 * a.ld_zx + a.d_ssm;
+    bf16_t* ring = reinterpret_cast<bf16_t*>(a.conv_ring) + (size_t)s.kv_row * MB_DC * conv_dim;
+    for (int c = threadIdx.x; c < conv_dim; c += 256) {
+#pragma unroll
+      for (int k = 0; k < MB_DC; ++k) {
+        const int qq = s.len - MB_DC + k;
+        if (qq >= 0) ring[(size_t)((s.pos0 + qq) & 3) * conv_dim + c] = zx0[(size_t)qq * a.ld_zx + c];
+        else if (s.pos0 == 0) ring[(size_t)(qq & 3) * conv_dim + c] = (bf16_t)0;
+      }
+    }
+    return;
+  }
+  if (s.pos0 <= 0) return;
+  constexpr int HV = MB_HD * MB_DS / 8;  // uint4 of one head's state
+  const size_t h = blockIdx.y;
+  const uint4* src = reinterpret_cast<const uint4*>(a.ssm) + ((size_t)s.kv_row * a.nheads + h) * HV;
+  uint4* dst = reinterpret_cast<uint4*>(h0s) + ((size_t)cont_rank(a, sqs, blockIdx.x) * a.nheads + h) * HV;
+  for (int i = threadIdx.x; i < HV; i += 256) dst[i] = src[i];
 }
 
 // PQ workgroups per (sequence, head), each 64 / PQ head dims; thread (p-group, n-block) owns PR = 4 / PQ rows p
@@ -259,7 +323,9 @@ extern "C" int zmi_scan_stamps_read(void* dst, size_t bytes) {
   } while (0)
 #endif
 
-template <int PQ>
+// CONT: a sequence with pos0 > 0 starts its registers from the bf16 state of its state row instead of 0. A workgroup
+// reads exactly the state rows it alone writes at the end, so the recurrence forms need no copy of h0.
+template <int PQ, bool CONT>
 __global__ __launch_bounds__(256) void mamba2_scan2_kernel(const ZmiMamba2Args a, const ScanSeqs sqs, const bf16_t* xc,
                                                            const float* dts, const float* das) {
   constexpr int PW = MB_HD / PQ, PR = PW / 16;  // head dims per workgroup, rows per thread
@@ -300,6 +366,18 @@ __global__ __launch_bounds__(256) void mamba2_scan2_kernel(const ZmiMamba2Args a
   for (int r = 0; r < PR; ++r)
 #pragma unroll
     for (int k = 0; k < 8; ++k) st[r][k] = 0.f;
+  if constexpr (CONT) {
+    if (sqs.seqs[sq.idx].pos0 > 0) {
+#pragma unroll
+      for (int r = 0; r < PR; ++r) {
+        const uint4 v = *reinterpret_cast<const uint4*>(reinterpret_cast<const bf16_t*>(a.ssm) +
+                                                        (((size_t)kv * a.nheads + h) * MB_HD + p0 + r) * MB_DS + nb * 8);
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) st[r][2 * e] = bf2f(w[e]), st[r][2 * e + 1] = bf2f(w[e] >> 16);
+      }
+    }
+  }
   bf16_t* y = reinterpret_cast<bf16_t*>(a.y);
   ZMI_SSTAMP(0);
   load(0);
@@ -444,8 +522,16 @@ __device__ __forceinline__ uint32_t split_bf16(float v, uint32_t* lo) {
   return h;
 }
 
+// CONT (zmi_mamba2_scan_cont): a sequence with pos0 > 0 continues from the bf16 state h0 (mamba2_carry_kernel's copy in
+// the workspace, h0s by cont_rank: neither role reads the state row the state role writes). Two more terms,
+//     y_t   += exp(cum[t]) (C_t . h0)      one more bf16 MFMA per y tile (C, h0 exactly bf16), fp32 sums; the wave's
+//                                           h0 fragments (16 p x 128 n, 4 uint4 per lane) stay in registers: the y
+//                                           role's LDS is full at T = 256
+//     state  = exp(cum[T-1]) h0 + W^T B    the accumulators start from the decayed h0
+// with cum in fp64 as everywhere. A sequence with pos0 == 0 reads no h0 and runs the arithmetic of the plain kernel.
+template <bool CONT>
 __global__ __launch_bounds__(SSD_NT) void mamba2_ssd_kernel(const ZmiMamba2Args a, const ScanSeqs sqs, const bf16_t* xc,
-                                                         const float* dts) {
+                                                         const float* dts, const bf16_t* h0s) {
   extern __shared__ __attribute__((aligned(16))) char smem[];  // sized for the launch's longest sequence
   __shared__ int seq_sh;
   const int role = blockIdx.x & 1, sh = blockIdx.x >> 1, h = sh % a.nheads;
@@ -460,6 +546,12 @@ __global__ __launch_bounds__(SSD_NT) void mamba2_ssd_kernel(const ZmiMamba2Args 
   const float Ah = a.A[h];
   const bool state_role = role == 1;
   const int s32 = L.S32;
+  bool cont = false;
+  const bf16_t* h0 = nullptr;
+  if constexpr (CONT) {
+    cont = sqs.seqs[sq.idx].pos0 > 0;
+    if (cont) h0 = h0s + ((size_t)cont_rank(a, sqs, sq.idx) * a.nheads + h) * MB_HD * MB_DS;
+  }
   bf16_t* Bs = reinterpret_cast<bf16_t*>(smem + L.b_off());
   // (1) B rows s < s_end (zero to s32) for both roles; dt and cum for every position (the same fixed-shape scan in
   // every role: lane L owns positions 4L .. 4L + 3)
@@ -516,6 +608,13 @@ __global__ __launch_bounds__(SSD_NT) void mamba2_ssd_kernel(const ZmiMamba2Args 
     };
     load_c(0);
     const float Dh = a.D[h];
+    uint4 hf[MB_DS / 32];  // CONT: h0 rows of the wave's p tile as MFMA B fragments (k over the state columns)
+    if (CONT && cont && wave < 8) {
+#pragma unroll
+      for (int kk = 0; kk < MB_DS / 32; ++kk)
+        hf[kk] = *reinterpret_cast<const uint4*>(h0 + (size_t)(16 * (wave >> 1) + (lane & 15)) * MB_DS + 32 * kk +
+                                                 8 * (lane >> 4));
+    }
     for (int t0 = 0; t0 < T; t0 += SSD_TB) {
       const int tn = min(SSD_TB, T - t0), s_end = t0 + tn, sk = (s_end + 31) / 32;  // k-blocks of 32 positions
 #pragma unroll
@@ -530,6 +629,17 @@ __global__ __launch_bounds__(SSD_NT) void mamba2_ssd_kernel(const ZmiMamba2Args 
       double ct[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) ct[i] = cum[t0 + 16 * (wave & 1) + 4 * (lane >> 4) + i];  // < S32 <= SSD_TMAX
+      // CONT: g0 = C_blk h0^T of this wave's y tile (t tile wave & 1, p tile wave >> 1), taken HERE, between the
+      // block's two barriers, where the C rows are stable: after the second barrier the waves that finish step (4)
+      // refill Cs with the next block's rows while others are still in (4), so (4) must not read Cs (the plain kernel's
+      // (4) reads only M and x). g0 waits in registers for the y tile.
+      f32x4_t g0 = {0.f, 0.f, 0.f, 0.f};
+      if (CONT && cont && wave < 8) {
+#pragma unroll
+        for (int kk = 0; kk < MB_DS / 32; ++kk)
+          g0 = mfma_bf16(*reinterpret_cast<const uint4*>(Cs + (16 * (wave & 1) + (lane & 15)) * SSD_BROW + 32 * kk +
+                                                         8 * (lane >> 4)), hf[kk], g0);
+      }
       for (int tile = wave; tile < 4 * sk; tile += SSD_NT / 64) {
         const int ti = tile & 1, si = tile >> 1;
         const bool live = 16 * ti < tn && 16 * si <= t0 + 16 * ti + 15;
@@ -569,6 +679,10 @@ __global__ __launch_bounds__(SSD_NT) void mamba2_ssd_kernel(const ZmiMamba2Args 
             const uint4 bv = gather8(Xs + (32 * kk + 8 * (lane >> 4)) * SSD_XROW + p, SSD_XROW);
             acc = mfma_bf16(*reinterpret_cast<const uint4*>(Mh + mo), bv, acc);
             acc = mfma_bf16(*reinterpret_cast<const uint4*>(Ml + mo), bv, acc);
+          }
+          if (CONT && cont) {  // + exp(cum[t]) (C_t . h0): g0 from step (3)'s phase, ct this wave's rows' cum
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc[i] += expf((float)ct[i]) * g0[i];
           }
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
@@ -616,6 +730,15 @@ __global__ __launch_bounds__(SSD_NT) void mamba2_ssd_kernel(const ZmiMamba2Args 
     f32x4_t acc[NPW];
 #pragma unroll
     for (int ni = 0; ni < NPW; ++ni) acc[ni] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    if (CONT && cont) {  // exp(cum[T-1]) h0
+      const float eT = expf((float)cT);
+#pragma unroll
+      for (int ni = 0; ni < NPW; ++ni)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          acc[ni][i] = eT * bf2f((uint32_t)reinterpret_cast<const uint16_t*>(
+                                h0)[(size_t)(16 * pi + 4 * (lane >> 4) + i) * MB_DS + 16 * (nb + ni) + (lane & 15)]);
+    }
     for (int kk = 0; kk < s32 / 32; ++kk) {
       const int r = 32 * kk + 8 * (lane >> 4);
       const uint4 ah = gather8(Wh + r * SSD_XROW + 16 * pi + (lane & 15), SSD_XROW);
@@ -673,10 +796,20 @@ extern "C" int64_t zmi_mamba2_scan_ws_bytes(int m, int d_ssm, int nheads) {
   return xc + 2 * (((int64_t)m * nheads * 4 + 255) / 256 * 256);
 }
 
+// + one bf16 state [nheads][64][128] per continuing sequence (pos0 > 0, len > 0): mamba2_carry_kernel's copies
+extern "C" int64_t zmi_mamba2_scan_cont_ws_bytes(int m, int d_ssm, int nheads, int n_cont) {
+  const int64_t base = zmi_mamba2_scan_ws_bytes(m, d_ssm, nheads);
+  if (base <= 0 || n_cont < 0) return 0;
+  return base + (int64_t)n_cont * nheads * MB_HD * MB_DS * 2;
+}
+
 namespace {
 
 // The conv + dt launch over the a->M rows, then the scan launches: n_ssd sequences in the SSD form (LDS for the
 // longest, t_max positions) and n_scan in mamba2_scan2_kernel<PQ>; `sq` says which rows are which sequence.
+// CONT (zmi_mamba2_scan_cont, ragged tables only): mamba2_carry_kernel between the conv launch and the scans, h0s its
+// copies of the continuing sequences' states.
+template <bool CONT>
 int launch_scan(const ZmiMamba2Args* a, ScanSeqs sq, int n_ssd, int t_max, int n_scan, int pq, void* ws,
                 hipStream_t s) {
   const int64_t xcb = ((int64_t)a->M * (a->d_ssm + 2 * MB_DS) * 2 + 255) / 256 * 256;
@@ -684,35 +817,41 @@ int launch_scan(const ZmiMamba2Args* a, ScanSeqs sq, int n_ssd, int t_max, int n
   bf16_t* xc = (bf16_t*)ws;
   float* dts = (float*)((char*)ws + xcb);
   float* das = (float*)((char*)ws + xcb + hb);
+  bf16_t* h0s = CONT ? (bf16_t*)((char*)ws + xcb + 2 * hb) : nullptr;
   const int conv_dim = a->d_ssm + 2 * MB_DS;
   sq.lo = 0, sq.hi = INT_MAX;
-  hipLaunchKernelGGL(mamba2_conv_kernel, dim3((unsigned)a->M, (unsigned)((conv_dim + 255) / 256)), dim3(256), 0, s, *a,
-                     sq, xc, dts, das);
+  hipLaunchKernelGGL(mamba2_conv_kernel<CONT>, dim3((unsigned)a->M, (unsigned)((conv_dim + 255) / 256)), dim3(256), 0,
+                     s, *a, sq, xc, dts, das);
   ZMI_CHECK(hipGetLastError());
+  if constexpr (CONT) {
+    hipLaunchKernelGGL(mamba2_carry_kernel, dim3((unsigned)sq.n_seq, (unsigned)(a->nheads + 1)), dim3(256), 0, s, *a,
+                       sq, h0s);
+    ZMI_CHECK(hipGetLastError());
+  }
   if (n_ssd > 0) {  // the quadratic (SSD) form
     const SsdLds L(t_max);
     const size_t lds = std::max(L.y_bytes(), L.s_bytes());
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&mamba2_ssd_kernel),
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&mamba2_ssd_kernel<CONT>),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize,
                                                        160 * 1024 - 16);  // the kernel's static LDS word comes off
     ZMI_CHECK(attr);
     sq.lo = 0, sq.hi = SSD_TMAX;
-    hipLaunchKernelGGL(mamba2_ssd_kernel, dim3((unsigned)((int64_t)n_ssd * a->nheads * 2)), dim3(SSD_NT), lds, s, *a,
-                       sq, (const bf16_t*)xc, (const float*)dts);
+    hipLaunchKernelGGL(mamba2_ssd_kernel<CONT>, dim3((unsigned)((int64_t)n_ssd * a->nheads * 2)), dim3(SSD_NT), lds, s,
+                       *a, sq, (const bf16_t*)xc, (const float*)dts, (const bf16_t*)h0s);
     ZMI_CHECK(hipGetLastError());
   }
   if (n_scan > 0) {
     sq.lo = pq == 0 ? SSD_TMAX : 0, sq.hi = INT_MAX;  // 0: the sequences past the quadratic form's reach
     const dim3 grid((unsigned)((int64_t)n_scan * a->nheads * (pq == 0 ? 4 : pq)));
     if (pq == 1)
-      hipLaunchKernelGGL(mamba2_scan2_kernel<1>, grid, dim3(256), 0, s, *a, sq, (const bf16_t*)xc, (const float*)dts,
-                         (const float*)das);
+      hipLaunchKernelGGL((mamba2_scan2_kernel<1, CONT>), grid, dim3(256), 0, s, *a, sq, (const bf16_t*)xc,
+                         (const float*)dts, (const float*)das);
     else if (pq == 2)
-      hipLaunchKernelGGL(mamba2_scan2_kernel<2>, grid, dim3(256), 0, s, *a, sq, (const bf16_t*)xc, (const float*)dts,
-                         (const float*)das);
+      hipLaunchKernelGGL((mamba2_scan2_kernel<2, CONT>), grid, dim3(256), 0, s, *a, sq, (const bf16_t*)xc,
+                         (const float*)dts, (const float*)das);
     else
-      hipLaunchKernelGGL(mamba2_scan2_kernel<4>, grid, dim3(256), 0, s, *a, sq, (const bf16_t*)xc, (const float*)dts,
-                         (const float*)das);
+      hipLaunchKernelGGL((mamba2_scan2_kernel<4, CONT>), grid, dim3(256), 0, s, *a, sq, (const bf16_t*)xc,
+                         (const float*)dts, (const float*)das);
     ZMI_CHECK(hipGetLastError());
   }
   return 0;
@@ -731,27 +870,36 @@ extern "C" int zmi_mamba2_scan_ws(const ZmiMamba2Args* a, int seq_len, void* ws,
   if (!scan_pq_ok(pq)) return zmi_fail_msg("mamba2_scan_ws: ZMI_OPT_SCAN_PQ must be 0, 1, 2 or 4");
   const bool ssd = pq == 0 && seq_len <= SSD_TMAX;
   const int n = a->M / seq_len;
-  return launch_scan(a, ScanSeqs{nullptr, 0, seq_len, 0, 0}, ssd ? n : 0, seq_len, ssd ? 0 : n, pq, ws,
+  return launch_scan<false>(a, ScanSeqs{nullptr, 0, seq_len, 0, 0}, ssd ? n : 0, seq_len, ssd ? 0 : n, pq, ws,
                      (hipStream_t)stream);
 }
 
-extern "C" int zmi_mamba2_scan_seqs(const ZmiMamba2Args* a, const ZmiAttnSeq* seqs, int n_seq,
-                                    const ZmiAttnSeq* seqs_host, void* ws, int64_t ws_bytes, void* stream) {
+namespace {
+
+// zmi_mamba2_scan_seqs (CONT false: every sequence from an empty state) and zmi_mamba2_scan_cont: the host checks on
+// the table's host copy, before any launch, then launch_scan
+template <bool CONT>
+int scan_table(const ZmiMamba2Args* a, const ZmiAttnSeq* seqs, int n_seq, const ZmiAttnSeq* seqs_host, void* ws,
+               int64_t ws_bytes, void* stream) {
+#define ZMI_SCAN_FAIL(text_) return zmi_fail_msg(CONT ? "mamba2_scan_cont: " text_ : "mamba2_scan_seqs: " text_)
   if (int e = check_mamba(a)) return e;
-  if (n_seq < 0) return zmi_fail_msg("mamba2_scan_seqs: n_seq < 0");
+  if (n_seq < 0) ZMI_SCAN_FAIL("n_seq < 0");
   if (n_seq > 0 && (!seqs || !seqs_host))
-    return zmi_fail_msg("mamba2_scan_seqs: the device table and its host copy are required");
+    ZMI_SCAN_FAIL("the device table and its host copy are required");
   const int pq = zmi_option(ZMI_OPT_SCAN_PQ);
-  if (!scan_pq_ok(pq)) return zmi_fail_msg("mamba2_scan_seqs: ZMI_OPT_SCAN_PQ must be 0, 1, 2 or 4");
+  if (!scan_pq_ok(pq)) ZMI_SCAN_FAIL("ZMI_OPT_SCAN_PQ must be 0, 1, 2 or 4");
   std::vector<std::pair<int, int>> rows, kvs;  // (first row, row past the last), (state row, index) of the live ones
-  int n_ssd = 0, n_scan = 0, t_max = 0;
+  int n_ssd = 0, n_scan = 0, t_max = 0, n_cont = 0;
   for (int i = 0; i < n_seq; ++i) {
     const ZmiAttnSeq& s = seqs_host[i];
-    if (s.len < 0 || s.q_row0 < 0) return zmi_fail_msg("mamba2_scan_seqs: negative len or q_row0");
-    if (s.q_row0 > a->M - s.len) return zmi_fail_msg("mamba2_scan_seqs: a sequence's rows end past M");
-    if (s.pos0 != 0) return zmi_fail_msg("mamba2_scan_seqs: pos0 must be 0 (prefill from an empty state)");
-    if (s.kv_row < 0) return zmi_fail_msg("mamba2_scan_seqs: negative kv_row");
+    if (s.len < 0 || s.q_row0 < 0) ZMI_SCAN_FAIL("negative len or q_row0");
+    if (s.q_row0 > a->M - s.len) ZMI_SCAN_FAIL("a sequence's rows end past M");
+    if (!CONT && s.pos0 != 0) ZMI_SCAN_FAIL("pos0 must be 0 (prefill from an empty state)");
+    if (CONT && s.pos0 < 0) ZMI_SCAN_FAIL("negative pos0");
+    if (CONT && s.pos0 > INT_MAX - s.len) ZMI_SCAN_FAIL("pos0 + len overflows");
+    if (s.kv_row < 0) ZMI_SCAN_FAIL("negative kv_row");
     if (s.len == 0) continue;
+    n_cont += s.pos0 > 0 ? 1 : 0;
     rows.emplace_back(s.q_row0, s.q_row0 + s.len);
     kvs.emplace_back(s.kv_row, i);
     if (pq == 0 && s.len <= SSD_TMAX) {
@@ -764,11 +912,26 @@ extern "C" int zmi_mamba2_scan_seqs(const ZmiMamba2Args* a, const ZmiAttnSeq* se
   std::sort(rows.begin(), rows.end());
   std::sort(kvs.begin(), kvs.end());
   for (size_t i = 1; i < rows.size(); ++i) {
-    if (rows[i].first < rows[i - 1].second) return zmi_fail_msg("mamba2_scan_seqs: two sequences share rows");
-    if (kvs[i].first == kvs[i - 1].first) return zmi_fail_msg("mamba2_scan_seqs: two sequences share a kv_row");
+    if (rows[i].first < rows[i - 1].second) ZMI_SCAN_FAIL("two sequences share rows");
+    if (kvs[i].first == kvs[i - 1].first) ZMI_SCAN_FAIL("two sequences share a kv_row");
   }
-  if (!ws || ws_bytes < zmi_mamba2_scan_ws_bytes(a->M, a->d_ssm, a->nheads))
-    return zmi_fail_msg("mamba2_scan_seqs: workspace smaller than zmi_mamba2_scan_ws_bytes");
+  if (!CONT && (!ws || ws_bytes < zmi_mamba2_scan_ws_bytes(a->M, a->d_ssm, a->nheads)))
+    ZMI_SCAN_FAIL("workspace smaller than zmi_mamba2_scan_ws_bytes");
+  if (CONT && (!ws || ws_bytes < zmi_mamba2_scan_cont_ws_bytes(a->M, a->d_ssm, a->nheads, n_cont)))
+    ZMI_SCAN_FAIL("workspace smaller than zmi_mamba2_scan_cont_ws_bytes");
   if (rows.empty()) return 0;
-  return launch_scan(a, ScanSeqs{seqs, n_seq, 0, 0, 0}, n_ssd, t_max, n_scan, pq, ws, (hipStream_t)stream);
+  return launch_scan<CONT>(a, ScanSeqs{seqs, n_seq, 0, 0, 0}, n_ssd, t_max, n_scan, pq, ws, (hipStream_t)stream);
+#undef ZMI_SCAN_FAIL
+}
+
+}  // namespace
+
+extern "C" int zmi_mamba2_scan_seqs(const ZmiMamba2Args* a, const ZmiAttnSeq* seqs, int n_seq,
+                                    const ZmiAttnSeq* seqs_host, void* ws, int64_t ws_bytes, void* stream) {
+  return scan_table<false>(a, seqs, n_seq, seqs_host, ws, ws_bytes, stream);
+}
+
+extern "C" int zmi_mamba2_scan_cont(const ZmiMamba2Args* a, const ZmiAttnSeq* seqs, int n_seq,
+                                    const ZmiAttnSeq* seqs_host, void* ws, int64_t ws_bytes, void* stream) {
+  return scan_table<true>(a, seqs, n_seq, seqs_host, ws, ws_bytes, stream);
 }

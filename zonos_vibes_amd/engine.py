@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from . import _lib, quant
+from .prefill_plan import ChunkPlanner, check_chunk
 from .prefill_table import PREFILL_ATTN, prefill_table
 from . import synthetic as syn
 from .config import EMB_VOCAB, HEAD_VOCAB, N_CODEBOOKS, ROPE_TABLE_LEN, ZonosConfig
@@ -719,11 +720,14 @@ class HipEngine:
             self._advance(k, s)
 
     # ------------------------------------------------------------------ prefill
-    def _prefill_check(self, cond: torch.Tensor, prefix: torch.Tensor | None, max_new_tokens: int) -> int:
+    def _prefill_check(self, cond: torch.Tensor, prefix: torch.Tensor | None, max_new_tokens: int,
+                       chunked: bool = False) -> int:
+        """The prompt's row count; chunked: it runs in chunks of at most max_prefill rows, so only the KV capacity
+        bounds it."""
         lc = cond.shape[1]
         p = 0 if prefix is None else int(prefix.shape[-1])
         s_len = lc + p + 1
-        if s_len > self.max_prefill:
+        if s_len > self.max_prefill and not chunked:
             raise ValueError(f"prefill length {s_len} > engine max_prefill {self.max_prefill}")
         if s_len + max_new_tokens + 8 > self.smax or p + max_new_tokens + 9 > self.tcap:
             raise ValueError("utterance longer than the engine's KV capacity")
@@ -740,12 +744,17 @@ class HipEngine:
         """The slot's sampling parameters, delayed-code buffer and granules, and its 2 x s_len prefill rows
         (cond, uncond) at row `off` of the prefill buffers (reference model.py:181-196, 240-250); in the single
         layout its one sequence of s_len rows, into KV row `slot`."""
+        self._prefill_stage_slot(slot, cond, prefix, max_new_tokens, params, s_len)
+        self._prefill_stage_rows(slot, cond, 0, s_len, off)
+
+    def _prefill_stage_slot(self, slot: int, cond: torch.Tensor, prefix: torch.Tensor | None, max_new_tokens: int,
+                            params: SamplingParams, s_len: int):
+        """Once per prompt: the slot's sampling parameters, its delayed-code buffer (zmi_delay_init) and its granules.
+        The slot stays inactive."""
         assert 0 <= slot < self.S
-        L, d = self.lib, self.d
         lc = cond.shape[1]
         p = s_len - lc - 1
         total = p + max_new_tokens + 9
-        cond = cond.to(self.dev, torch.bfloat16)
         pr = torch.zeros(N_CODEBOOKS, max(p, 1), dtype=torch.int32, device=self.dev)
         if p:
             pr[:, :p] = prefix.reshape(N_CODEBOOKS, p).to(self.dev, torch.int32)
@@ -753,22 +762,37 @@ class HipEngine:
         sz = ctypes.sizeof(_lib.Sampling)
         self.params[slot * sz:(slot + 1) * sz].copy_(cp)
         self.slot_greedy[slot] = params.temperature <= 0
-        _lib.check(L.zmi_delay_init(ctypes.byref(self.slots), slot, pr.data_ptr(), p, total, self.sptr), "delay")
+        _lib.check(self.lib.zmi_delay_init(ctypes.byref(self.slots), slot, pr.data_ptr(), p, total, self.sptr), "delay")
         self._reset_granules(slot)  # no granule of an earlier utterance may match a tag
-        rps = self.rps
-        xp = self.x_pre[off: off + rps * s_len]
-        codes = self.delayed[slot]
-        ar = torch.arange(s_len, dtype=torch.int32, device=self.dev)
-        for half in range(rps):
-            xp[half * s_len: half * s_len + lc] = cond[half]
-            _lib.check(L.zmi_embed_codes(codes.data_ptr(), self.tcap, p + 1, self.w["emb"].data_ptr(), d,
-                                         xp[half * s_len + lc].data_ptr(), d, self.sptr), "embed_codes")
-            self.row_pos_pre[off + half * s_len: off + (half + 1) * s_len] = ar
-            self.row_kv_pre[off + half * s_len: off + (half + 1) * s_len] = rps * slot + half
 
-    def _prefill_finish(self, slot: int, max_new_tokens: int, off: int, s_len: int, p: int, noise):
-        """Heads of the slot's last prefill rows, slot state, first sample + frame write (model.py:251-264)."""
-        self._prefill_logits(s_len) if off == 0 else self._prefill_logits(s_len, off)
+    def _prefill_stage_rows(self, slot: int, cond: torch.Tensor, a: int, b: int, off: int):
+        """Per chunk: rows a .. b - 1 of the slot's prompt (conditioning rows, then the embedded frames of its delayed
+        codes) for each of its sequences, rows_per_slot x (b - a) rows from row `off` of the prefill buffers, with
+        their positions (a .. b - 1) and KV rows. The whole prompt is a = 0, b = s_len."""
+        L, d = self.lib, self.d
+        lc = cond.shape[1]
+        n = b - a
+        cond = cond.to(self.dev, torch.bfloat16)
+        rps = self.rps
+        xp = self.x_pre[off: off + rps * n]
+        codes = self.delayed[slot]
+        ar = torch.arange(a, b, dtype=torch.int32, device=self.dev)
+        nc = max(min(b, lc) - a, 0)  # conditioning rows in the chunk
+        f0 = max(a, lc) - lc         # its first frame
+        for half in range(rps):
+            if nc:
+                xp[half * n: half * n + nc] = cond[half][a: a + nc]
+            if n > nc:
+                _lib.check(L.zmi_embed_codes(codes.data_ptr() + 4 * f0, self.tcap, n - nc, self.w["emb"].data_ptr(), d,
+                                             xp[half * n + nc].data_ptr(), d, self.sptr), "embed_codes")
+            self.row_pos_pre[off + half * n: off + (half + 1) * n] = ar
+            self.row_kv_pre[off + half * n: off + (half + 1) * n] = rps * slot + half
+
+    def _prefill_finish(self, slot: int, max_new_tokens: int, off: int, s_len: int, p: int, noise, rows=None):
+        """Heads of the slot's last prefill rows, slot state, first sample + frame write (model.py:251-264). rows: the
+        rows each of its sequences has in the pass (a prompt's last chunk; default the whole prompt, s_len)."""
+        n = s_len if rows is None else rows
+        self._prefill_logits(n) if off == 0 else self._prefill_logits(n, off)
         vals = {"active": 1, "pos": s_len, "offset": p, "remaining": max_new_tokens + 8, "stopping": 0,
                 "step": 0, "total_len": p + max_new_tokens + 9}
         for k, v in vals.items():
@@ -777,8 +801,11 @@ class HipEngine:
         self.pos_hi[slot] = s_len
 
     def prefill(self, slot: int, cond: torch.Tensor, prefix: torch.Tensor | None, max_new_tokens: int,
-                params: SamplingParams, noise: torch.Tensor | None = None):
-        """_prefill + first sample + frame write (reference model.py:240-264) for one slot."""
+                params: SamplingParams, noise: torch.Tensor | None = None, prefill_chunk: int | None = None):
+        """_prefill + first sample + frame write (reference model.py:240-264) for one slot. prefill_chunk: see
+        prefill_many."""
+        if check_chunk(prefill_chunk, self.max_prefill) is not None:
+            return self.prefill_many([(slot, cond, prefix, max_new_tokens, params)], prefill_chunk, noise)[0]
         s_len = self._prefill_check(cond, prefix, max_new_tokens)
         p = s_len - cond.shape[1] - 1
         self.stream.wait_stream(torch.cuda.current_stream(self.dev))
@@ -788,14 +815,31 @@ class HipEngine:
             self._prefill_finish(slot, max_new_tokens, 0, s_len, p, noise)
         return s_len
 
-    def prefill_many(self, items) -> list:
+    def prefill_many(self, items, prefill_chunk: int | None = None, noise: torch.Tensor | None = None) -> list:
         """prefill() of several slots: items are (slot, cond, prefix, max_new_tokens, params). Their rows are
         packed (rows_per_slot x s_len each, so the single layout admits twice as many utterances to a pass)
         into passes of up to `pre_rows` rows, each pass through the layers once (one weight stream for
         all of them). Every kernel's per-row arithmetic is independent of the rows beside it (the GEMV / GEMM /
         split-K forms and the attention are tested batch-invariant), so each slot decodes exactly as if it had
-        been prefilled alone (generate_batch == generate)."""
+        been prefilled alone (generate_batch == generate).
+
+        prefill_chunk = C (1 <= C <= max_prefill; None: everything above, and a prompt past max_prefill is refused): a
+        prompt of s_len rows runs as chunks [k C, min((k + 1) C, s_len)), planned by prefill_plan.ChunkPlanner, so
+        s_len is bounded by the KV capacity alone. A later chunk attends the KV rows the earlier ones wrote (the tiled
+        attention from pos0 = k C) and, on the hybrid, continues the Mamba2 scan from the state row
+        (zmi_mamba2_scan_cont). A prompt of at most C rows is one chunk from position 0 and keeps its bits. (noise:
+        the first sample's, with a single item, as prefill() takes it.)"""
         items = list(items)
+        chunk = check_chunk(prefill_chunk, self.max_prefill)
+        if chunk is not None:
+            if not self.prefill_batch and len(items) > 1:  # (an instance that loops: one prompt's passes at a time)
+                return [self.prefill_many([it], chunk)[0] for it in items]
+            planner = self.chunk_planner(chunk)
+            self.stream.wait_stream(torch.cuda.current_stream(self.dev))
+            lens = [self.chunked_admit(planner, *it, noise=noise if len(items) == 1 else None) for it in items]
+            while planner.pending:
+                self.chunked_pass(planner)
+            return lens
         if not self.prefill_batch or len(items) <= 1:
             return [self.prefill(*it) for it in items]
         lens = [self._prefill_check(it[1], it[2], it[3]) for it in items]
@@ -818,6 +862,43 @@ class HipEngine:
                 for (slot, cond, prefix, mnt, params), s_len, off in g:
                     self._prefill_finish(slot, mnt, off, s_len, s_len - cond.shape[1] - 1, None)
         return lens
+
+    # ---- chunked prefill, pass by pass (prefill_many(prefill_chunk=C) runs the passes back to back; a serving
+    # session runs one in front of a round of decode steps)
+    def chunk_planner(self, chunk: int) -> ChunkPlanner:
+        """A planner for this engine's pass size and current row layout; it holds the prompts in flight."""
+        return ChunkPlanner(self.pre_rows, self.rps, check_chunk(chunk, self.max_prefill))
+
+    def chunked_admit(self, planner: ChunkPlanner, slot: int, cond: torch.Tensor, prefix: torch.Tensor | None,
+                      max_new_tokens: int, params: SamplingParams, noise: torch.Tensor | None = None) -> int:
+        """Stage the slot once (it stays inactive until its last chunk has run) and queue its prompt's chunks. A slot
+        cancelled mid-prompt is taken off with planner.drop(slot) (and released by the caller)."""
+        s_len = self._prefill_check(cond, prefix, max_new_tokens, chunked=True)
+        self.stream.wait_stream(torch.cuda.current_stream(self.dev))
+        with torch.cuda.stream(self.stream):
+            self._prefill_stage_slot(slot, cond, prefix, max_new_tokens, params, s_len)
+        planner.add(slot, s_len, (cond, s_len, max_new_tokens, noise))
+        return s_len
+
+    def chunked_pass(self, planner: ChunkPlanner) -> list:
+        """One pass through the layers over the planner's next chunks -> the slots whose prompt it completed (their
+        first frame is sampled and they are active)."""
+        ps = planner.next_pass()
+        if ps is None:
+            return []
+        done = []
+        self.stream.wait_stream(torch.cuda.current_stream(self.dev))
+        with torch.cuda.stream(self.stream):
+            for en in ps.entries:
+                self._prefill_stage_rows(en.slot, en.job[0], en.begin, en.end, en.off)
+            self._prefill_layers(ps.rows, ps.max_pos, ps.seqs(self.rps))
+            for en in ps.entries:
+                if en.last:
+                    cond, s_len, mnt, noise = en.job
+                    self._prefill_finish(en.slot, mnt, en.off, s_len, s_len - cond.shape[1] - 1, noise,
+                                         rows=en.end - en.begin)
+                    done.append(en.slot)
+        return done
 
     def _reset_granules(self, slot: int):
         """Zero the in-launch hand-off granules of the slot's rows (tags are positions + 1)."""

@@ -10,7 +10,8 @@ hipGraph-captured decode loop, slots — is HipEngine's; this class only swaps t
   Mamba2 block   zmi_mamba_block: in_proj GEMV + the Mamba2 step (conv ring + SiLU + selective state
                  update) in one launch, granule hand-off (zmi_mamba2_step as its own launch above 16 rows)
                  -> out_proj GEMV with the GRMS prologue (RMSNormGated; prefill: zmi_gated_rmsnorm and
-                 zmi_mamba2_scan_seqs over the pass's ragged sequences)
+                 zmi_mamba2_scan_seqs over the pass's ragged sequences, zmi_mamba2_scan_cont where a pass
+                 holds a later chunk of a prompt)
   MHA block      QKV GEMV (non-interleaved rotary as interleaved pairs on permuted q / k rows, bf16
                  cos / sin as flash-attn caches them) -> attention kernel -> out_proj GEMV
   optional MLP   (add + LayerNorm) fc1 SwiGLU GEMV -> fc2 GEMV       (d_intermediate > 0)
@@ -246,7 +247,7 @@ class HybridEngine(HipEngine):
     def _layer_items(self, lw, m, x, hid, nrm, zx, yb, yn, hm, q, attn, row_kv, row_pos, first, scan=None,
                      max_pos=None, table=None):
         """Launches of one block over m rows (decode: scan None; prefill: scan = the pass's sequence table as
-        (device pointer, host int32 [n_seq][4]), the rows' ragged sequences from position 0)."""
+        (device pointer, host int32 [n_seq][4], whether a sequence continues from its state row))."""
         d, md, qd = self.d, self.md, self.H * self.hd
         items = [("call", self._addln(None if first else hid, x, (lw["ln1_w"], lw["ln1_b"]), nrm, m))]
         if lw["kind"] == "attn":
@@ -268,9 +269,11 @@ class HybridEngine(HipEngine):
             else:
                 a = self._mamba_args(lw, zx, yb, m, row_pos, row_kv)
                 lib, s, wp, wn = self.lib, self.sptr, self.scan_ws.data_ptr(), self.scan_ws.numel()
-                sp, sa = scan
-                items.append(("call", lambda a=a: _lib.check(lib.zmi_mamba2_scan_seqs(
-                    ctypes.byref(a), sp, len(sa), sa.ctypes.data, wp, wn, s), "mamba2_scan_seqs")))
+                sp, sa, cont = scan
+                name = "mamba2_scan_cont" if cont else "mamba2_scan_seqs"
+                fn = getattr(lib, "zmi_" + name)
+                items.append(("call", lambda a=a: _lib.check(fn(
+                    ctypes.byref(a), sp, len(sa), sa.ctypes.data, wp, wn, s), name)))
             items.append(("call", self._gnorm(lw, yb, zx, yn, m)))
             items.append(("gemv", self._gemv(lw["out"], yn, m, d, md["d_ssm"], _lib.EPI_STORE, hid, d)))
         if lw.get("ff"):
@@ -369,19 +372,32 @@ class HybridEngine(HipEngine):
         return self._plans[(rows, form)]
 
     # ------------------------------------------------------------------ prefill
+    def chunk_planner(self, chunk: int):
+        """HipEngine.chunk_planner, and the scan workspace sized once for chunked passes: zmi_mamba2_scan_cont copies
+        the state of every continuing sequence of a pass (at most one chunk per slot, so 2 x slots sequences, and no
+        more than a pass has rows). Nothing is then allocated in front of a round."""
+        planner = super().chunk_planner(chunk)
+        need = int(self.lib.zmi_mamba2_scan_cont_ws_bytes(self.pre_rows, self.md["d_ssm"], self.md["nheads"],
+                                                          min(self.R, self.pre_rows)))
+        if self.scan_ws.numel() < need:
+            with torch.cuda.stream(self.stream):
+                self.scan_ws = torch.zeros(need, dtype=torch.uint8, device=self.dev)
+        return planner
+
     def _prefill_layers(self, m: int, max_pos: int, seqs):
         """The m rows of one pass through every layer. seqs: the rows' sequences as ZmiAttnSeq rows (q_row0, len,
-        kv_row, pos0), any lengths, every one from position 0 (Mamba2.forward from an empty cache; the reference's
-        step() takes one token at a time after that). One table, built and copied once per pass, serves the MHA
-        layers' tiled attention (HipEngine._prefill_table) and the Mamba2 layers' scan (zmi_mamba2_scan_seqs)."""
+        kv_row, pos0), any lengths. One table, built and copied once per pass, serves the MHA layers' tiled attention
+        (HipEngine._prefill_table) and the Mamba2 layers' scan. A pass whose sequences all start at position 0
+        (Mamba2.forward from an empty cache) runs zmi_mamba2_scan_seqs; a pass with a later chunk of a prompt (pos0 > 0,
+        chunked prefill) runs zmi_mamba2_scan_cont, which continues those sequences from their state rows and gives
+        the pass's starting sequences zmi_mamba2_scan_seqs's bits (its larger workspace: chunk_planner)."""
         seqs = list(seqs)
         sa = np.ascontiguousarray(np.asarray(seqs, dtype=np.int64).reshape(-1, 4), dtype=np.int32)
-        if (sa[:, 3] != 0).any():
-            raise ValueError("hybrid prefill: every sequence starts at position 0")
+        cont = bool((sa[:, 3] != 0).any())
         table = self._prefill_table(seqs)
         # the attention's device table begins with the sequence rows; prefill_attn = "rows" has none, so copy them
         sdev = table[0] if table is not None else torch.from_numpy(sa.ravel()).to(self.dev)
-        scan = (sdev.data_ptr(), sa)
+        scan = (sdev.data_ptr(), sa, cont)
         for i, lw in enumerate(self.w["layers"]):
             for kind, item in self._layer_items(lw, m, self.x_pre, self.hid_pre, self.nrm_pre, self.zx_pre,
                                                 self.yb_pre, self.yn_pre, self.hm_pre, self.q_pre, self.attn_pre,

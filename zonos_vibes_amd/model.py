@@ -28,6 +28,7 @@ from .autoencoder import DACAutoencoder
 from .conditioning import PrefixConditioner
 from .config import N_CODEBOOKS, ZonosConfig
 from .engine import ST_FIELDS, SamplingParams, codes_count, make_engine
+from .prefill_plan import check_chunk
 from .serving import BatchRounds, ServeSession
 
 
@@ -117,6 +118,17 @@ class Zonos:
             self.engine.w = w
             self.engine._build_plan()
 
+    def _prefill_rows(self, need_pre: int, prefill_chunk) -> int:
+        """The prefill rows a call asks of the engine: with prefill_chunk = C a prompt runs C rows at a time, so a long
+        prompt asks for C rows, not its length (and no longer rebuilds the engine)."""
+        chunk = check_chunk(prefill_chunk)
+        return need_pre if chunk is None else min(need_pre, chunk)
+
+    def _engine_chunk(self, prefill_chunk):
+        """prefill_chunk as the engine takes it (<= its max_prefill). After _ensure_capacity(_prefill_rows(...)) a
+        larger value means that every prompt of the call fits one chunk, so the boundaries do not change."""
+        return None if prefill_chunk is None else min(int(prefill_chunk), self.engine.max_prefill)
+
     def _select_layout(self, cfg_scale: float) -> int:
         """The engine's row layout for a call (after _ensure_capacity, which may have rebuilt the engine): single
         (one row per utterance) for cfg_scale == 1, the reference's guidance-free branch, else paired."""
@@ -175,23 +187,25 @@ class Zonos:
                  sampling_params: dict = dict(min_p=0.1), progress_bar: bool = True,
                  disable_torch_compile: bool = False,
                  callback: Callable[[torch.Tensor, int, int], bool] | None = None,
-                 chunk: int = 64) -> torch.Tensor:
+                 chunk: int = 64, prefill_chunk: int | None = None) -> torch.Tensor:
         """Reference model.py:218-315 (batch_size=1). `disable_torch_compile` is accepted and ignored:
         the decode step is a hipGraph of hand-written kernels in every mode. cfg_scale == 1: the guidance-free
         branch (model.py:112), one row through the backbone; prefix_conditioning [1, Lc, d], or [2, Lc, d] of which
-        row 0 is used."""
+        row 0 is used. prefill_chunk = C: the prompt (Lc + P + 1 rows) goes through the layers C rows at a time
+        (HipEngine.prefill_many), so a long audio prefix needs C prefill rows, not its length; None: one pass."""
         self._check_not_serving("generate")
         if batch_size != 1 or not self._cond_rows_ok(prefix_conditioning, cfg_scale):
             raise ValueError("the reference generate() supports batch_size=1 only (SURVEY.md §0.3); "
                              "use generate_batch() for many utterances")
         lc = prefix_conditioning.shape[1]
         p = 0 if audio_prefix_codes is None else audio_prefix_codes.shape[2]
-        self._ensure_capacity(1, lc + p + max_new_tokens + 9, lc + p + 1)
+        self._ensure_capacity(1, lc + p + max_new_tokens + 9, self._prefill_rows(lc + p + 1, prefill_chunk))
         self._select_layout(cfg_scale)
         e = self.engine
         params = SamplingParams.from_dict(dict(sampling_params), cfg_scale, _draw_seed())
         slot = 0
-        e.prefill(slot, prefix_conditioning, audio_prefix_codes, max_new_tokens, params)
+        e.prefill(slot, prefix_conditioning, audio_prefix_codes, max_new_tokens, params,
+                  prefill_chunk=self._engine_chunk(prefill_chunk))
         max_steps = max_new_tokens + 8
         bar = None
         if progress_bar:
@@ -229,7 +243,8 @@ class Zonos:
     @torch.inference_mode()
     def stream(self, prefix_conditioning: torch.Tensor, audio_prefix_codes: torch.Tensor | None = None,
                max_new_tokens: int = 86 * 30, cfg_scale: float = 2.0, sampling_params: dict = dict(min_p=0.1),
-               chunk_frames: int = 16, sample_rate: int | None = None, decoder: str = "window"):
+               chunk_frames: int = 16, sample_rate: int | None = None, decoder: str = "window",
+               prefill_chunk: int | None = None):
         """generate() + autoencoder.decode() as a generator of waveform chunks [1, 1, 512 n] fp32 (device): audio
         is yielded while the utterance is still being generated. With the same torch.manual_seed, the chunks
         concatenated are bit for bit decode(generate(...)) (batch 1, generate()'s arguments).
@@ -249,7 +264,7 @@ class Zonos:
         True)): the same chunks, each decoded at the cost of its own frames; a round's rollback point then holds a
         copy of the decoder's state.
 
-        cfg_scale == 1: guidance-free, as generate(cfg_scale=1)."""
+        cfg_scale == 1: guidance-free, as generate(cfg_scale=1). prefill_chunk: as generate(prefill_chunk=)."""
         self._check_not_serving("stream")
         carry = self._decoder_mode(decoder)
         rate = self._output_rate(sample_rate)
@@ -260,7 +275,7 @@ class Zonos:
             raise ValueError("chunk_frames >= 1")
         lc = prefix_conditioning.shape[1]
         p = 0 if audio_prefix_codes is None else audio_prefix_codes.shape[2]
-        self._ensure_capacity(1, lc + p + max_new_tokens + 9, lc + p + 1)
+        self._ensure_capacity(1, lc + p + max_new_tokens + 9, self._prefill_rows(lc + p + 1, prefill_chunk))
         self._select_layout(cfg_scale)
         e = self.engine
         params = SamplingParams.from_dict(dict(sampling_params), cfg_scale, _draw_seed())
@@ -310,7 +325,8 @@ class Zonos:
 
         ae = self.autoencoder
         try:
-            e.prefill(slot, prefix_conditioning, audio_prefix_codes, max_new_tokens, params)
+            e.prefill(slot, prefix_conditioning, audio_prefix_codes, max_new_tokens, params,
+                      prefill_chunk=self._engine_chunk(prefill_chunk))
             queue = [launch(0)]  # audio-prefix frames are final before any decode step
             while queue:
                 if steps < max_steps:  # keep the engine one round ahead of the host
@@ -354,9 +370,12 @@ class Zonos:
     def generate_batch(self, conds: Sequence[torch.Tensor], prefixes: Sequence[torch.Tensor | None] | None = None,
                        max_new_tokens: Sequence[int] | int = 86 * 30, cfg_scale: float = 2.0,
                        sampling_params: dict = dict(min_p=0.1), seeds: Sequence[int] | None = None,
-                       max_slots: int | None = None, chunk: int = 32) -> list[torch.Tensor]:
+                       max_slots: int | None = None, chunk: int = 32,
+                       prefill_chunk: int | None = None) -> list[torch.Tensor]:
         """Many independent utterances through the engine's slots; result i equals generate() on utterance i.
-        cfg_scale == 1: guidance-free (one row per utterance, so a step of k busy slots runs k rows, not 2 k)."""
+        cfg_scale == 1: guidance-free (one row per utterance, so a step of k busy slots runs k rows, not 2 k).
+        prefill_chunk = C: every prompt runs C rows at a time (result i equals generate(prefill_chunk=C) on utterance
+        i: a prompt's chunk boundaries do not depend on its batch mates)."""
         self._check_not_serving("generate_batch")
         n = len(conds)
         prefixes = list(prefixes) if prefixes is not None else [None] * n
@@ -365,9 +384,10 @@ class Zonos:
         need_seq = max(c.shape[1] + (0 if p is None else p.shape[2]) + m + 9 for c, p, m in zip(conds, prefixes, mnt))
         need_pre = max(c.shape[1] + (0 if p is None else p.shape[2]) + 1 for c, p in zip(conds, prefixes))
         slots = min(max_slots or n, n)
-        self._ensure_capacity(slots, need_seq, need_pre)
+        self._ensure_capacity(slots, need_seq, self._prefill_rows(need_pre, prefill_chunk))
         self._select_layout(cfg_scale)
         e = self.engine
+        pchunk = self._engine_chunk(prefill_chunk)
         # longest-processing-time first, so the tail is short
         order = sorted(range(n), key=lambda i: -mnt[i])
         queue = list(order)
@@ -384,7 +404,7 @@ class Zonos:
                     items.append((s, conds[i], prefixes[i], mnt[i], params))
                     owner[s] = i
                     remaining[s] = mnt[i] + 8
-            e.prefill_many(items)  # the free slots' prefills in as few passes through the layers as fit
+            e.prefill_many(items, pchunk)  # the free slots' prefills in as few passes through the layers as fit
 
         # a step runs slots 0 .. the highest busy one (rounded up to a few sizes, one decode graph each): LPT
         # fills the low slots with the longest utterances, so the tail of a job steps a handful of rows instead
@@ -414,7 +434,7 @@ class Zonos:
                      max_new_tokens: Sequence[int] | int = 86 * 30, cfg_scale: float = 2.0,
                      sampling_params: dict = dict(min_p=0.1), seeds: Sequence[int] | None = None,
                      max_slots: int | None = None, chunk_frames: int = 16, sample_rate: int | None = None,
-                     decoder: str = "window"):
+                     decoder: str = "window", prefill_chunk: int | None = None):
         """generate_batch() + autoencoder.decode() per utterance as a generator of (utterance index, waveform chunk
         [1, 1, 512 n] fp32 (device), last): every utterance's audio is yielded while it and the others are still being
         generated. With the same seeds, utterance i's chunks concatenated are bit for bit
@@ -435,7 +455,9 @@ class Zonos:
 
         decoder: "window" (the default) or "carry", the carried-state DAC decoder (autoencoder.stream_decoder_batch(
         carry=True)): the same items; the slots that push equal frame counts past their start are one launch sequence
-        whatever their positions, and a round decodes the frames it made final, not their windows."""
+        whatever their positions, and a round decodes the frames it made final, not their windows.
+
+        prefill_chunk: as generate_batch(prefill_chunk=)."""
         self._check_not_serving("stream_batch")
         carry = self._decoder_mode(decoder)
         rate = self._output_rate(sample_rate)
@@ -451,9 +473,10 @@ class Zonos:
         need_seq = max(c.shape[1] + p + m + 9 for c, p, m in zip(conds, plen, mnt))
         need_pre = max(c.shape[1] + p + 1 for c, p in zip(conds, plen))
         slots = min(max_slots or n, n)
-        self._ensure_capacity(slots, need_seq, need_pre)
+        self._ensure_capacity(slots, need_seq, self._prefill_rows(need_pre, prefill_chunk))
         self._select_layout(cfg_scale)
         e, ae = self.engine, self.autoencoder
+        pchunk = self._engine_chunk(prefill_chunk)
         key = (id(ae), int(chunk_frames), carry)
         dec = self._stream_batch_decoders.get(key)
         if dec is None or dec.lanes < slots:  # kept: its graphs and stage buffers serve every later call
@@ -476,7 +499,7 @@ class Zonos:
                     rounds.start(s, plen[i], mnt[i])
                     if rs is not None:
                         rs.reset(s)
-            e.prefill_many(items)
+            e.prefill_many(items, pchunk)
 
         try:
             fill()
@@ -497,7 +520,7 @@ class Zonos:
 
     def serve(self, max_slots: int, max_seqlen: int, max_prefill: int, chunk_frames: int = 16,
               pcm16: bool = False, sample_rate: int | None = None, decoder: str = "window",
-              guidance: bool = True) -> ServeSession:
+              guidance: bool = True, prefill_chunk: int | None = None) -> ServeSession:
         """A serving session (serving.ServeSession, a context manager): submit() requests from any thread while
         others are being spoken, run_round() from one thread hands out every ticket's chunks, each ticket's
         concatenated bit for bit decode(generate_batch()) of the request alone; with pcm16 they leave as int16 CPU
@@ -507,10 +530,14 @@ class Zonos:
         open generate(), stream(), generate_batch(), stream_batch() and another serve() raise RuntimeError.
         guidance=False opens a guidance-free session (the single layout, one row per slot): its submit() takes
         cfg_scale=1 only, and conditioning [1, Lc, d] or [2, Lc, d]. A session is one or the other; guided and
-        guidance-free requests do not mix in one session."""
+        guidance-free requests do not mix in one session.
+        prefill_chunk = C (1 <= C <= max_prefill): a request's prompt runs C rows at a time, at most one pass in front
+        of a round while any ticket is decoding, so a prompt longer than max_prefill is admitted (the KV capacity,
+        max_seqlen, still bounds it) and the running tickets' audio waits for one chunk, not for the whole prompt. Every
+        ticket's chunks are then decode(generate_batch(..., prefill_chunk=C)) of the request alone."""
         self._check_not_serving("serve")
         return ServeSession(self, max_slots, max_seqlen, max_prefill, chunk_frames, pcm16, sample_rate, decoder,
-                            guidance)
+                            guidance, prefill_chunk)
 
     @staticmethod
     def _decoder_mode(decoder: str) -> bool:

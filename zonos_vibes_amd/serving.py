@@ -43,10 +43,13 @@ class SlotScheduler:
     the one thread that drives the engine."""
 
     def __init__(self, max_slots: int, max_seqlen: int, max_prefill: int, d_model: int | None = None,
-                 guidance: bool = True):
+                 guidance: bool = True, prefill_chunk: int | None = None):
+        from .prefill_plan import check_chunk
         if max_slots < 1:
             raise ValueError("max_slots >= 1")
         self.max_slots, self.max_seqlen, self.max_prefill = int(max_slots), int(max_seqlen), int(max_prefill)
+        # chunked prefill: a prompt runs prefill_chunk rows at a time, so max_prefill no longer bounds a request
+        self.prefill_chunk = check_chunk(prefill_chunk, self.max_prefill)
         self.d_model = d_model
         self.guidance = bool(guidance)  # False: a guidance-free session, conditioning [1, Lc, d] too
         self._cond = threading.Condition()
@@ -74,7 +77,7 @@ class SlotScheduler:
             raise ValueError("max_new_tokens >= 1")
         if lc + p + n + 9 > self.max_seqlen:
             raise ValueError(f"Lc + P + max_new_tokens + 9 = {lc + p + n + 9} > the session's max_seqlen {self.max_seqlen}")
-        if lc + p + 1 > self.max_prefill:
+        if lc + p + 1 > self.max_prefill and self.prefill_chunk is None:
             raise ValueError(f"Lc + P + 1 = {lc + p + 1} > the session's max_prefill {self.max_prefill}")
         return lc, p
 
@@ -330,7 +333,7 @@ class ServeSession:
 
     def __init__(self, model, max_slots: int, max_seqlen: int, max_prefill: int, chunk_frames: int = 16,
                  pcm16: bool = False, sample_rate: int | None = None, decoder: str = "window",
-                 guidance: bool = True):
+                 guidance: bool = True, prefill_chunk: int | None = None):
         if chunk_frames < 1:
             raise ValueError("chunk_frames >= 1")
         carry = model._decoder_mode(decoder)
@@ -339,7 +342,8 @@ class ServeSession:
             raise RuntimeError("a serve() session is already open on this model")
         self.model, self.pcm16 = model, bool(pcm16)
         self.guidance = bool(guidance)
-        self.sched = SlotScheduler(max_slots, max_seqlen, max_prefill, model.config.backbone.d_model, self.guidance)
+        self.sched = SlotScheduler(max_slots, max_seqlen, max_prefill, model.config.backbone.d_model, self.guidance,
+                                   prefill_chunk)
         model._ensure_capacity(max_slots, max_seqlen, max_prefill)  # once: a session never rebuilds the engine
         model._select_layout(2.0 if self.guidance else 1)  # the session's layout, for as long as it is open
         e, ae = model.engine, model.autoencoder
@@ -353,6 +357,10 @@ class ServeSession:
         self.rs = None if rate is None else model._stream_resampler(rate, max_slots)  # kept, every lane reset
         self.rounds = BatchRounds(e, ae, dec, max_slots, chunk_frames, self.rs)
         self.egress = Pcm16Egress(e.dev, max_slots, chunk_frames) if self.pcm16 else None
+        # chunked prefill: the prompts in flight (prefill_plan.ChunkPlanner) and their slots, occupied but inactive
+        self.planner = None if self.sched.prefill_chunk is None else e.chunk_planner(self.sched.prefill_chunk)
+        self.mid: dict = {}  # slot -> Request of the slots mid-prompt
+        self.passes_run = 0
         self.rounds_run = 0
         self._open = True
         model._serving = self
@@ -387,7 +395,9 @@ class ServeSession:
 
     # ---- the driving thread
     def run_round(self) -> list:
-        """One round: cancellations, admissions (one prefill_many), the steps, and the round's audio as
+        """One round: cancellations, admissions (one prefill_many; with prefill_chunk the admitted prompts are queued and
+        _prefill_passes runs their chunks, a slot mid-prompt being occupied but inactive: not stepped as busy, no
+        items), the steps, and the round's audio as
         [(ticket, chunk, last)]: fp32 device tensors [1, 1, 512 n] as stream_batch() yields them, or with pcm16
         int16 CPU tensors; with sample_rate a chunk has any length >= 0. [] at once when nothing is running or
         waiting."""
@@ -402,13 +412,17 @@ class ServeSession:
                 if self.rs is not None:
                     self.rs.reset(s)
                 e.release(s)
-            if admitted:
+                if self.mid.pop(s, None) is not None:  # cancelled mid-prompt: its remaining chunks are dropped
+                    self.planner.drop(s)
+            if admitted and self.planner is None:
                 e.prefill_many([(s, *r.payload[:2], r.max_new_tokens, r.payload[2]) for s, r in admitted])
                 for s, r in admitted:
                     rounds.start(s, r.p, r.max_new_tokens)
                     if self.rs is not None:
                         self.rs.reset(s)
-            busy = self.sched.busy()
+            elif self.planner is not None:
+                self._prefill_passes(admitted)
+            busy = [(s, r) for s, r in self.sched.busy() if s not in self.mid]
             if not busy:
                 return []
             owner = dict(busy)
@@ -425,6 +439,27 @@ class ServeSession:
             return [(owner[s].ticket, chunks[s], s in live) for s in chunks
                     if live.get(s, True) and owner[s].ticket not in gone]
 
+    def _prefill_passes(self, admitted):
+        """Chunked prefill's share of a round: the admitted requests are staged (occupied, inactive) and queued; while
+        any ticket is decoding, at most ONE pass runs in front of the round's steps, so its audio waits for a chunk and
+        not for a prompt; when none is decoding, passes run back to back until a slot starts. A slot whose last chunk
+        has run starts its round bookkeeping (rounds.start) and decodes from this round on."""
+        e = self.model.engine
+        for s, r in admitted:
+            e.chunked_admit(self.planner, s, *r.payload[:2], r.max_new_tokens, r.payload[2])
+            self.mid[s] = r
+        decoding = any(s not in self.mid for s, _ in self.sched.busy())
+        while self.planner.pending:
+            done = e.chunked_pass(self.planner)
+            self.passes_run += 1
+            for s in done:
+                r = self.mid.pop(s)
+                self.rounds.start(s, r.p, r.max_new_tokens)
+                if self.rs is not None:
+                    self.rs.reset(s)
+            if decoding or done:
+                break
+
     def close(self):
         """Reset every DAC lane, release every busy slot, and let the model's other entry points run again."""
         if not self._open:
@@ -438,6 +473,9 @@ class ServeSession:
                     self.rs.reset(s)
             for s in busy:
                 self.model.engine.release(s)
+            if self.planner is not None:
+                self.planner.clear()
+                self.mid.clear()
         finally:
             self.model._serving = None
 
