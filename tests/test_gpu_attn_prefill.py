@@ -13,7 +13,7 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 HD = 128
 SENTINEL = -77.0  # exact in bf16; no attention output of these inputs equals it in every element of a row
-HEADS = [(16, 4), (4, 1), (8, 4)]
+HEADS = [(16, 4), (4, 1), (8, 4), (4, 4)]
 
 
 def _lib():

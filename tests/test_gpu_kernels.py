@@ -311,7 +311,7 @@ def test_attention_matches_reference_blocking(positions):
     _check_attention(out, q, kc, vc, positions)
 
 
-@pytest.mark.parametrize("hq,hkv", [(16, 4), (4, 1), (8, 4)])
+@pytest.mark.parametrize("hq,hkv", [(16, 4), (4, 1), (8, 4), (4, 4)])
 def test_attention_whole_query_variant_bit_identical_to_chunked(hq, hkv):
     """The whole-query kernel (one workgroup per (query, kv head, dim slice), no cross-workgroup
     exchange) restates the chunked kernel's arithmetic operation for operation: identical bits at
@@ -335,7 +335,7 @@ def test_attention_whole_query_variant_bit_identical_to_chunked(hq, hkv):
 
 
 @pytest.mark.parametrize("variant", [2, 3, 5])
-@pytest.mark.parametrize("hq,hkv", [(16, 4), (4, 1), (8, 4)])
+@pytest.mark.parametrize("hq,hkv", [(16, 4), (4, 1), (8, 4), (4, 4)])
 def test_attention_split_launch_variants_bit_identical_to_one_launch(hq, hkv, variant):
     """Variant 2 (scores + maxima launch, then the finish launch, no waiting inside either), variant 3 (the
     same, the merge as a third launch) and variant 5 (one workgroup per 512-key block) against variant 1 (one
