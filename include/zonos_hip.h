@@ -50,8 +50,15 @@ enum { ZMI_PRO_AUTO = 0, ZMI_PRO_ADDLN = 2, ZMI_PRO_GRMS = 3, ZMI_PRO_GRMS_G = 4
  *         packed column; layout M8F8 (zonos_vibes_amd/quant.py pack_m8f8): the bytes of the M8 chunks 2p and 2p + 1 of
  *         a column group share one 1 KiB piece, lane l holding its 8 weights of chunk 2p then its 8 of chunk 2p + 1.
  *         Every 2^w_exp q is a bf16 value, and zmi_gemv_launch returns the bits of the BF16 launch on those dequantised
- *         weights. Built for the plain / LayerNorm prologue, K in {512, 1024, 2048, 8192} and the SWIGLU, RESIDUAL and
- *         F32 epilogues (the MLP projections); zmi_gemv_launch only: the split-K GEMM and the fused blocks refuse it. */
+ *         weights. Built for
+ *           - the SWIGLU, RESIDUAL and F32 epilogues with the plain / LayerNorm prologue, K in {512, 1024, 2048, 8192}
+ *             (the MLP projections);
+ *           - the STORE epilogue of the Mamba2 mixers' projections: in_proj under ADDLN (K 512 / 2048, any M), out_proj
+ *             under GRMS / GRMS_G (K 1024 / 4096, M <= 4) or plain at K 1024 / 4096 (any M). A plain STORE launch at
+ *             K 512 / 2048 / 8192, the QKV and LOGITS epilogues and the LayerNorm prologue with STORE are refused;
+ *           - zmi_mamba_block / zmi_mamba_block_pf (the in_proj role; a kernel of its own name).
+ *         The split-K GEMM, the many-row form and zmi_attn_block read bf16 only: a prefill expands a projection with
+ *         zmi_unpack_fp8 and runs the bf16 forms on the result. */
 enum { ZMI_WFMT_BF16 = 0, ZMI_WFMT_FP8 = 1 };
 
 typedef struct ZmiGemvArgs {
@@ -83,6 +90,10 @@ typedef struct ZmiGemvArgs {
 } ZmiGemvArgs;
 
 int zmi_pack_weight(const void* src, void* dst, int n_src, int k, int n_pad, int mode, void* stream);
+/* Expand an FP8 weight (n_pad * k bytes in layout M8F8, int8 w_exp[n_pad] in packed column order) into the bf16 layout
+ * M8 (2 * n_pad * k bytes at m8_out): byte for byte zmi_pack_weight of the dequantised weight 2^w_exp q. n_pad % 8 == 0,
+ * k % 128 == 0, both weights 16-byte aligned. A streaming kernel (16 bytes in, 32 out per lane): no reduction, exact. */
+int zmi_unpack_fp8(const void* m8f8, const void* w_exp, int n_pad, int k, void* m8_out, void* stream);
 /* One kernel for every M: a row's result is bit-identical whatever the batch it is computed in. */
 int zmi_gemv_launch(const ZmiGemvArgs* args, int epi, void* stream);
 /* The launch form zmi_gemv_launch(args, epi) would take, computed by the code it dispatches on; launches nothing and
@@ -582,7 +593,8 @@ int zmi_gated_rmsnorm(const void* y, int ldy, const void* z, int ldz, int m, int
  * workgroups load their state / conv-ring / conv-weight operands under the in_proj's weight stream and take
  * the in_proj output from {pair, tag = position + 1} granules (`gran`: zmi_mamba_block_gran_words(M,
  * d_in_proj) words, zeroed when a row starts an utterance); 1 <= M <= 16; bit-identical to the two
- * separate launches; *err becomes nonzero if a wait timed out. */
+ * separate launches; *err becomes nonzero if a wait timed out. in_proj->w_fmt may be ZMI_WFMT_FP8 (w_exp set, 8-byte
+ * aligned): the bits of the BF16 block on the dequantised weights. */
 int zmi_mamba_block(const ZmiGemvArgs* in_proj, const ZmiMamba2Args* step, void* gran, unsigned* err, void* stream);
 int64_t zmi_mamba_block_gran_words(int rows, int d_in_proj);
 /* zmi_mamba_block plus `prefetch->blocks` prefetch-only workgroups (ZmiPrefetch, as zmi_attn_block_pf) that
@@ -608,7 +620,9 @@ int zmi_graph_destroy(void* graph_exec);
 const char* zmi_last_error(void);
 /* ABI version, bumped whenever a weight layout or an option's meaning changes: 4 = channel-blocked DAC conv weights
  * [tap][ci / 32][co][32] (zmi_dac_conv / conv_t / conv_out) and the round-5 ZMI_OPT_GEMM_ROWS bits; 5 =
- * ZMI_OPT_XC_HANDOFF and zmi_xcd_dealing; 6 = ZMI_PRO_GRMS_G and ZmiMamba2Args.gz_g; 7 = the zmi_dac_*_lanes entry points. Check it before packing weights (zonos_vibes_amd/_lib.py refuses a library
+ * ZMI_OPT_XC_HANDOFF and zmi_xcd_dealing; 6 = ZMI_PRO_GRMS_G and ZmiMamba2Args.gz_g; 7 = the zmi_dac_*_lanes entry points.
+ * (zmi_unpack_fp8 and the FP8 forms of the Mamba2 projections were added at version 10: no layout, struct or option
+ * changed meaning, and every launch a version-10 caller could make gives what it gave.) Check it before packing weights (zonos_vibes_amd/_lib.py refuses a library
  * whose version differs). */
 int zmi_version(void);
 /* 1 if this device deals a launch's workgroups round-robin over its XCDs (blocks b and b + 8 on one XCD, 8

@@ -121,6 +121,7 @@ COND_EMBED, COND_VECTOR, COND_FOURIER, COND_LINEAR, COND_PASSTHROUGH = range(5)
 
 _SIGS = {
     "zmi_pack_weight": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "zmi_unpack_fp8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "zmi_gemv_launch": (c_int, [ctypes.POINTER(GemvArgs), c_int, c_void_p]),
     "zmi_gemv_form": (c_int, [ctypes.POINTER(GemvArgs), c_int, ctypes.POINTER(GemvForm)]),
     "zmi_layernorm_rows": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_int,

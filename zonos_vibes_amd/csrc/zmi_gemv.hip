@@ -41,6 +41,33 @@ __global__ void pack_kernel(const bf16_t* __restrict__ src, uint4* __restrict__ 
   dst[idx] = v;
 }
 
+// Expand an fp8 weight (layout M8F8 + one int8 exponent per packed column, quant.py) into the bf16 layout M8: the
+// bytes zmi_pack_weight gives for the dequantised weight 2^e q. A thread takes one lane of a 1 KiB M8F8 piece (g, p):
+// its 16 bytes are column 8g + (l & 7)'s 8 weights of the 64-k chunks 2p and 2p + 1, which are lane l of the M8
+// chunks (g, 2p) and (g, 2p + 1). E4M3 -> f32 is exact, 2^e q is a normal bf16 or a signed zero (quant.py), so the
+// product's high half is the weight. No reduction: nothing to round.
+__global__ void unpack_fp8_kernel(const uint4* __restrict__ src, const signed char* __restrict__ w_exp,
+                                  uint4* __restrict__ dst, int n_pad, int k) {
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const int np = k >> 7;  // pieces per group
+  const size_t total = (size_t)(n_pad >> 3) * np * 64;
+  if (idx >= total) return;
+  const int l = idx & 63;
+  const size_t t = idx >> 6;
+  const int p = (int)(t % np), g = (int)(t / np);
+  const float scale = __uint_as_float((uint32_t)((int)w_exp[g * 8 + (l & 7)] + 127) << 23);
+  const uint4 q = src[idx];
+  auto pair = [&](uint32_t d, bool hi) {  // two E4M3 bytes -> two scaled bf16
+    const auto f = hi ? __builtin_amdgcn_cvt_pk_f32_fp8((int)d, true) : __builtin_amdgcn_cvt_pk_f32_fp8((int)d, false);
+    return (__float_as_uint(f[0] * scale) >> 16) | (__float_as_uint(f[1] * scale) & 0xffff0000u);
+  };
+  const uint4 c0 = {pair(q.x, false), pair(q.x, true), pair(q.y, false), pair(q.y, true)};
+  const uint4 c1 = {pair(q.z, false), pair(q.z, true), pair(q.w, false), pair(q.w, true)};
+  uint4* o = dst + ((size_t)g * (2 * np) + 2 * p) * 64 + l;
+  o[0] = c0;
+  o[64] = c1;
+}
+
 }  // namespace
 
 // the argument checks of zmi_gemv_launch (0 = accepted; else zmi_last_error is set)
@@ -62,12 +89,15 @@ static int check_args(const ZmiGemvArgs& a, int epi) {
   if (epi == ZMI_EPI_QKV && (a.hd % 8 || a.smax <= 0 || !a.row_pos || !a.row_kv || !a.rope))
     return zmi_fail_msg("gemv: the QKV epilogue needs row_pos, row_kv, rope, smax and hd % 8 == 0");
   if (a.w_fmt != ZMI_WFMT_BF16 && a.w_fmt != ZMI_WFMT_FP8) return zmi_fail_msg("gemv: unknown weight format");
-  if (a.w_fmt == ZMI_WFMT_FP8 &&
-      (!a.w_exp || ((size_t)a.w_exp & 7) || a.pro != ZMI_PRO_AUTO || a.K == 4096 ||
-       (epi != ZMI_EPI_SWIGLU && epi != ZMI_EPI_RESIDUAL && epi != ZMI_EPI_F32)))
-    return zmi_fail_msg("gemv: fp8 weights need w_exp (8-byte aligned) and are built for the plain / LayerNorm prologue, "
-                        "K = 512, 1024, 2048 or 8192 and the SWIGLU, RESIDUAL and F32 epilogues");
   if (epi < ZMI_EPI_STORE || epi > ZMI_EPI_F32) return zmi_fail_msg("gemv: unknown epilogue");
+  if (a.w_fmt == ZMI_WFMT_FP8) {  // ZMI_PRO_* = PRO_*; ZMI_PRO_AUTO: LayerNorm with ln_w, else plain
+    const int pro = a.pro != ZMI_PRO_AUTO ? a.pro : (a.ln_w ? zmi_gemv::PRO_LN : zmi_gemv::PRO_PLAIN);
+    if (!a.w_exp || ((size_t)a.w_exp & 7) || !zmi_gemv::pro_built(a.K, epi, pro, true))
+      return zmi_fail_msg("gemv: fp8 weights need w_exp (8-byte aligned) and are built for the SWIGLU, RESIDUAL and F32 "
+                          "epilogues with the plain / LayerNorm prologue (K = 512, 1024, 2048 or 8192), and for the STORE "
+                          "epilogue with ADDLN (K = 512 or 2048), GRMS / GRMS_G (K = 1024 or 4096) or plain rows at "
+                          "K = 1024 or 4096");
+  }
   return 0;
 }
 
@@ -109,6 +139,18 @@ extern "C" int zmi_pack_weight(const void* src, void* dst, int n_src, int k, int
   const size_t total = (size_t)(n_pad / 8) * (k / 64) * 64;
   hipLaunchKernelGGL(pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)src, (uint4*)dst, n_src, k, n_pad, mode);
+  ZMI_CHECK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int zmi_unpack_fp8(const void* m8f8, const void* w_exp, int n_pad, int k, void* m8_out, void* stream) {
+  if (!m8f8 || !w_exp || !m8_out || n_pad < 8 || n_pad % 8 || k < 128 || k % 128 || ((size_t)m8f8 & 15) ||
+      ((size_t)m8_out & 15))
+    return zmi_fail_msg("unpack_fp8: n_pad % 8, k % 128, 16-byte aligned weights, w_exp set");
+  const size_t total = (size_t)(n_pad / 8) * (k / 128) * 64;
+  if ((total + 255) / 256 > 0x7fffffffu) return zmi_fail_msg("unpack_fp8: weight too large");
+  hipLaunchKernelGGL(unpack_fp8_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const uint4*)m8f8, (const signed char*)w_exp, (uint4*)m8_out, n_pad, k);
   ZMI_CHECK(hipGetLastError());
   return 0;
 }

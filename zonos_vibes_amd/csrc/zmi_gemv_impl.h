@@ -557,8 +557,8 @@ __device__ __forceinline__ void gemv_body(const ZmiGemvArgs& a, int n_cb, int n_
   constexpr int CHB = F8 ? 512 : 1024;    // bytes of a 64-k x 8-column weight chunk
   constexpr int NWL = F8 ? NL / 2 : NL;   // 16-byte weight loads per lane
   static_assert(FMT == ZMI_WFMT_BF16 || F8, "weight format");
-  static_assert(!F8 || (NL % 2 == 0 && FUSE == 0 && (PRO == PRO_PLAIN || PRO == PRO_LN)),
-                "fp8 weights: the MLP projections' plain / LayerNorm launches");
+  static_assert(!F8 || (NL % 2 == 0 && (FUSE == 0 || FUSE == 2)),
+                "fp8 weights: every prologue; the plain hand-offs and zmi_mamba_block's granule store");
   static_assert(RT == 8 || RT == 16, "row tile");
   static_assert(!FUSE || EPI == ZMI_EPI_QKV || EPI == ZMI_EPI_STORE || FUSE == 3, "in-launch hand-off: QKV or plain store");
   static_assert(FUSE != 2 || NTW, "the store hand-off runs on single-tile (decode) launches");
@@ -948,12 +948,17 @@ inline bool rows_launch(const ZmiGemvArgs& a) {
 // (4, 4, 8, 16) one is built as the plain tile loop only (groups_for's many-row plain case)
 #define ZMI_GEMV_SHAPES(X) X(1, 2, 4, 16) X(1, 4, 4, 16) X(1, 4, 8, 16) X(2, 4, 8, 16) X(1, 4, 16, 16) X(1, 8, 16, 8) X(2, 8, 16, 8)
 
-// the prologue of a shape, where it is built: fp8 weights for LayerNorm'd or plain rows and not for K = 4096 (no fp8
-// projection has it); ADDLN (the hybrid blocks' d_model GEMVs) for K 512 / 2048; GRMS (the Mamba2 out_proj, K = d_ssm)
-// for K 1024 / 4096 with the store epilogue, GRMS_G (the same from g = y * gate rows) on one tile (decode)
+// the prologue of a shape, where it is built: ADDLN (the hybrid blocks' d_model GEMVs) for K 512 / 2048; GRMS (the
+// Mamba2 out_proj, K = d_ssm) for K 1024 / 4096 with the store epilogue, GRMS_G (the same from g = y * gate rows) on one
+// tile (decode). fp8 weights: the MLP projections (SWIGLU / RESIDUAL / F32, LayerNorm'd or plain rows, not K = 4096)
+// and the Mamba2 mixers' projections with the store epilogue: in_proj under ADDLN only, out_proj under GRMS / GRMS_G
+// or plain at K = d_ssm (1024 / 4096; no other projection has that K). QKV and LOGITS read bf16 only.
 constexpr bool pro_built(int K, int epi, int pro, bool f8) {
-  if (pro == PRO_ADDLN) return !f8 && (K == 512 || K == 2048) && epi != ZMI_EPI_RESIDUAL && epi != ZMI_EPI_F32;
-  if (pro == PRO_GRMS || pro == PRO_GRMSG) return !f8 && (K == 1024 || K == 4096) && epi == ZMI_EPI_STORE;
+  if (f8 && epi != ZMI_EPI_STORE && epi != ZMI_EPI_SWIGLU && epi != ZMI_EPI_RESIDUAL && epi != ZMI_EPI_F32) return false;
+  if (pro == PRO_ADDLN)
+    return (K == 512 || K == 2048) && epi != ZMI_EPI_RESIDUAL && epi != ZMI_EPI_F32 && (!f8 || epi == ZMI_EPI_STORE);
+  if (pro == PRO_GRMS || pro == PRO_GRMSG) return (K == 1024 || K == 4096) && epi == ZMI_EPI_STORE;
+  if (f8 && epi == ZMI_EPI_STORE) return pro == PRO_PLAIN && (K == 1024 || K == 4096);
   return !f8 || K != 4096;
 }
 
@@ -975,8 +980,7 @@ inline bool form_for(const ZmiGemvArgs& a, int epi, ZmiGemvForm* f) {
   if (!shape_for(a.K, &sh)) return false;
   const bool f8 = a.w_fmt == ZMI_WFMT_FP8;
   // fp8 weights run gemv_body's tile loop for every M: the many-row form (and the split-K GEMM) read bf16 weights
-  // only. All forms agree bit for bit, so this costs many-row speed, never bits.
-  if (f8 && epi != ZMI_EPI_SWIGLU && epi != ZMI_EPI_RESIDUAL && epi != ZMI_EPI_F32) return false;
+  // only. All forms agree bit for bit, so this costs many-row speed, never bits. (Which fp8 launches exist: pro_built.)
   if (rows_launch(a)) {
     const int n_cb = (a.N / 8 + GR_G - 1) / GR_G, n_rt = (a.M + GR_RT - 1) / GR_RT;
     *f = {(zmi_option(ZMI_OPT_GEMM_ROWS) & 2) ? ZMI_FORM_ROWS_DENSE : ZMI_FORM_ROWS, GR_G, 4, 8, GR_RT, 0, PRO_PLAIN,
@@ -1036,15 +1040,15 @@ hipError_t launch_g(const ZmiGemvArgs& a, hipStream_t s, const ZmiGemvForm& f) {
   constexpr int K = W * NL * 64;
   constexpr bool F8 = FMT == ZMI_WFMT_FP8;
   if constexpr (pro_built(K, EPI, PRO_ADDLN, F8))
-    if (f.pro == PRO_ADDLN) return launch_tiles<G, W, NL, RT, PRO_ADDLN, EPI>(a, s, f);
+    if (f.pro == PRO_ADDLN) return launch_tiles<G, W, NL, RT, PRO_ADDLN, EPI, FMT>(a, s, f);
   if constexpr (pro_built(K, EPI, PRO_GRMS, F8)) {
-    if (f.pro == PRO_GRMS) return launch_tiles<G, W, NL, RT, PRO_GRMS, EPI>(a, s, f);
-    if (f.pro == PRO_GRMSG && f.ntw) return launch_p<G, W, NL, RT, PRO_GRMSG, EPI, 1>(a, s, f);
+    if (f.pro == PRO_GRMS) return launch_tiles<G, W, NL, RT, PRO_GRMS, EPI, FMT>(a, s, f);
+    if (f.pro == PRO_GRMSG && f.ntw) return launch_p<G, W, NL, RT, PRO_GRMSG, EPI, 1, FMT>(a, s, f);
   }
-  if constexpr (pro_built(K, EPI, PRO_LN, F8)) {
+  if constexpr (pro_built(K, EPI, PRO_LN, F8))
     if (f.pro == PRO_LN) return launch_tiles<G, W, NL, RT, PRO_LN, EPI, FMT>(a, s, f);
+  if constexpr (pro_built(K, EPI, PRO_PLAIN, F8))
     if (f.pro == PRO_PLAIN) return launch_tiles<G, W, NL, RT, PRO_PLAIN, EPI, FMT>(a, s, f);
-  }
   return hipErrorInvalidValue;
 }
 
@@ -1064,7 +1068,11 @@ hipError_t launch_rows(const ZmiGemvArgs& a, hipStream_t s, const ZmiGemvForm& f
 // gemv_body's launches of one weight format
 template <int EPI, int FMT>
 hipError_t launch_shape(const ZmiGemvArgs& a, hipStream_t s, const ZmiGemvForm& f) {
-  if (f.G == 4) return launch_p<4, 4, 8, 16, PRO_PLAIN, EPI, 0, FMT>(a, s, f);
+  if (f.G == 4) {
+    if constexpr (pro_built(2048, EPI, PRO_PLAIN, FMT == ZMI_WFMT_FP8))
+      return launch_p<4, 4, 8, 16, PRO_PLAIN, EPI, 0, FMT>(a, s, f);
+    return hipErrorInvalidValue;
+  }
 #define ZMI_SHAPE(G_, W_, NL_, RT_) \
   if (f.G == G_ && f.W == W_ && f.NL == NL_ && f.RT == RT_) return launch_g<G_, W_, NL_, RT_, EPI, FMT>(a, s, f);
   ZMI_GEMV_SHAPES(ZMI_SHAPE)
@@ -1079,7 +1087,7 @@ hipError_t launch(const ZmiGemvArgs& a, hipStream_t s) {
   if (f.kind == ZMI_FORM_ROWS_DENSE) return launch_rows<EPI, 1, true>(a, s, f);
   if (f.kind == ZMI_FORM_ROWS) return launch_rows<EPI, 2, false>(a, s, f);
   if (a.w_fmt == ZMI_WFMT_FP8) {
-    if constexpr (EPI == ZMI_EPI_SWIGLU || EPI == ZMI_EPI_RESIDUAL || EPI == ZMI_EPI_F32)
+    if constexpr (EPI == ZMI_EPI_STORE || EPI == ZMI_EPI_SWIGLU || EPI == ZMI_EPI_RESIDUAL || EPI == ZMI_EPI_F32)
       return launch_shape<EPI, ZMI_WFMT_FP8>(a, s, f);
     return hipErrorInvalidValue;
   }

@@ -52,10 +52,11 @@ constexpr unsigned SPIN = 1u << 20;
   } while (0)
 #endif
 
-__global__ __launch_bounds__(NT) void mamba_block_kernel(const ZmiGemvArgs ia, int n_cb, int n_in,
-                                                         const ZmiMamba2Args ma, uint64_t* gran, int gstride,
-                                                         unsigned* err, const ZmiPrefetch pf, int n_pf, int xc_l2) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+// the launch's three roles; FMT: the in_proj weights' format (the step and prefetch roles do not depend on it)
+template <int FMT>
+__device__ __forceinline__ void mamba_block_body(const ZmiGemvArgs& ia, int n_cb, int n_in, const ZmiMamba2Args& ma,
+                                                 uint64_t* gran, int gstride, unsigned* err, const ZmiPrefetch& pf,
+                                                 int n_pf, int xc_l2, char* smem) {
   const int b = blockIdx.x;
   if (b < n_in) {
     zmi_gemv::QkvFuse fz{gran, gstride};
@@ -74,7 +75,7 @@ __global__ __launch_bounds__(NT) void mamba_block_kernel(const ZmiGemvArgs ia, i
       }
       fz.l2_cols = 2 * ma.d_ssm;
     }
-    zmi_gemv::gemv_body<IG, IW, INL, IRT, zmi_gemv::PRO_ADDLN, ZMI_EPI_STORE, 1, 2>(ia, n_cb, 1, cb, smem, fz);
+    zmi_gemv::gemv_body<IG, IW, INL, IRT, zmi_gemv::PRO_ADDLN, ZMI_EPI_STORE, 1, 2, FMT>(ia, n_cb, 1, cb, smem, fz);
     return;
   }
   const int n_step = ma.M * ma.nheads;
@@ -146,6 +147,20 @@ __global__ __launch_bounds__(NT) void mamba_block_kernel(const ZmiGemvArgs ia, i
   ZMI_MSTAMP(6);
 }
 
+__global__ __launch_bounds__(NT) void mamba_block_kernel(const ZmiGemvArgs ia, int n_cb, int n_in,
+                                                         const ZmiMamba2Args ma, uint64_t* gran, int gstride,
+                                                         unsigned* err, const ZmiPrefetch pf, int n_pf, int xc_l2) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  mamba_block_body<ZMI_WFMT_BF16>(ia, n_cb, n_in, ma, gran, gstride, err, pf, n_pf, xc_l2, smem);
+}
+// the same launch over an fp8 in_proj (a kernel of its own name: the bf16 kernel keeps its in traces and profiles)
+__global__ __launch_bounds__(NT) void mamba_block_kernel_f8(const ZmiGemvArgs ia, int n_cb, int n_in,
+                                                            const ZmiMamba2Args ma, uint64_t* gran, int gstride,
+                                                            unsigned* err, const ZmiPrefetch pf, int n_pf, int xc_l2) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  mamba_block_body<ZMI_WFMT_FP8>(ia, n_cb, n_in, ma, gran, gstride, err, pf, n_pf, xc_l2, smem);
+}
+
 }  // namespace
 
 extern "C" int64_t zmi_mamba_block_gran_words(int rows, int d_in_proj) {
@@ -158,7 +173,10 @@ extern "C" int zmi_mamba_block_pf(const ZmiGemvArgs* in_proj, const ZmiMamba2Arg
   const ZmiMamba2Args& s = *step;
   if (a.K != 2048 || a.pro != ZMI_PRO_ADDLN || !a.ln_w || !a.ln_b || !a.aux || a.ld_aux % 8 || a.res_out == a.aux)
     return zmi_fail_msg("mamba_block: in_proj must be the ADDLN GEMV with K = 2048");
-  if (a.w_fmt != ZMI_WFMT_BF16) return zmi_fail_msg("mamba_block: bf16 weights only");
+  if (a.w_fmt != ZMI_WFMT_BF16 && a.w_fmt != ZMI_WFMT_FP8) return zmi_fail_msg("mamba_block: unknown weight format");
+  const bool f8 = a.w_fmt == ZMI_WFMT_FP8;
+  if (f8 && (!a.w_exp || ((size_t)a.w_exp & 7)))
+    return zmi_fail_msg("mamba_block: fp8 in_proj weights need w_exp (8-byte aligned)");
   if (a.M < 1 || a.M > IRT || s.M != a.M) return zmi_fail_msg("mamba_block: 1 <= M <= 16 rows, the same in both");
   if (s.headdim != MB_HD || s.d_state != MB_DS || s.d_conv != MB_DC || s.ngroups != 1 || s.nheads <= 0 ||
       s.d_ssm != s.nheads * MB_HD)
@@ -179,11 +197,14 @@ extern "C" int zmi_mamba_block_pf(const ZmiGemvArgs* in_proj, const ZmiMamba2Arg
                     (2 * s.d_ssm + 2 * MB_DS + s.nheads) / 16 - 2 * s.d_ssm / 16 <= 24 ? 1 : 0;
   const size_t lds = std::max(zmi_gemv::Img<2048>::bytes(a.M, IG * IW, IRT, zmi_gemv::PRO_ADDLN), (size_t)2560);
   if (lds > zmi_gemv::LDS_MAX) return zmi_fail_msg("mamba_block: LDS image too large");
-  if (lds > 64 * 1024) {
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&mamba_block_kernel),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                       (int)zmi_gemv::LDS_MAX);
-    if (attr != hipSuccess) return zmi_fail(attr, "hipFuncSetAttribute", __FILE__, __LINE__);
+  const auto kernel = f8 ? &mamba_block_kernel_f8 : &mamba_block_kernel;
+  if (lds > 64 * 1024) {  // once per kernel: allow > 64 KiB of dynamic LDS
+    static const hipError_t attr[2] = {
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&mamba_block_kernel),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)zmi_gemv::LDS_MAX),
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&mamba_block_kernel_f8),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)zmi_gemv::LDS_MAX)};
+    if (attr[f8] != hipSuccess) return zmi_fail(attr[f8], "hipFuncSetAttribute", __FILE__, __LINE__);
   }
   ZmiPrefetch pf{};
   if (prefetch) {
@@ -191,7 +212,7 @@ extern "C" int zmi_mamba_block_pf(const ZmiGemvArgs* in_proj, const ZmiMamba2Arg
     if (zmi_prefetch_invalid(pf)) return zmi_fail_msg("mamba_block: bad prefetch ranges");
   }
   const int n_pf = (pf.bytes[0] > 0 || pf.bytes[1] > 0) ? pf.blocks : 0;
-  hipLaunchKernelGGL(mamba_block_kernel, dim3((unsigned)(n_in + a.M * s.nheads + n_pf)), dim3(NT), lds,
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(n_in + a.M * s.nheads + n_pf)), dim3(NT), lds,
                      (hipStream_t)stream, a, n_cb, n_in, s, (uint64_t*)gran, a.N / 2, err, pf, n_pf, xc_l2);
   ZMI_CHECK(hipGetLastError());
   return 0;

@@ -503,7 +503,7 @@ class HipEngine:
                     pf = _lib.Prefetch()
                     if self.prefetch_blocks > 0:
                         if not oproj:  # (the fused out_proj role loads its weights itself)
-                            pf.ptr[0], pf.bytes[0] = lw["out"].data_ptr(), lw["out"].numel() * 2
+                            pf.ptr[0], pf.bytes[0] = lw["out"].data_ptr(), lw["out"].numel() * lw["out"].element_size()
                         if self.prefetch_second == "qkv":
                             nw = w["heads"] if i + 1 == len(w["layers"]) else w["layers"][i + 1]["qkv"]
                         else:
@@ -518,7 +518,7 @@ class HipEngine:
                     apf = None
                     if self.attn_prefetch_blocks > 0:
                         apf = _lib.Prefetch()
-                        apf.ptr[0], apf.bytes[0] = lw["out"].data_ptr(), lw["out"].numel() * 2
+                        apf.ptr[0], apf.bytes[0] = lw["out"].data_ptr(), lw["out"].numel() * lw["out"].element_size()
                         apf.ptr[1] = lw["fc1"].data_ptr()
                         apf.bytes[1] = min(lw["fc1"].numel() * lw["fc1"].element_size(),
                                            int(self.attn_prefetch_fc1_mb * 2 ** 20))
@@ -1052,11 +1052,28 @@ def check_weights(weights: str, hybrid: bool) -> None:
                                   "the hybrid engine takes bf16 weights only")
 
 
+def has_mamba2_mixers(cfg: ZonosConfig) -> bool:
+    """Whether the config's backbone has Mamba2 layers (a hybrid config whose layers are not all attention)."""
+    bb = cfg.backbone
+    return bool(bb.ssm_cfg) and len(set(int(i) for i in bb.attn_layer_idx)) < bb.n_layer
+
+
+def check_mixer_weights(mixer_weights: str, cfg: ZonosConfig) -> None:
+    """The engines' `mixer_weights` argument: "bf16", or "fp8" for the Mamba2 mixers' in_proj / out_proj (hybrid
+    backbones). Separate from `weights`, which names the MLP projections' format and keeps refusing the hybrid."""
+    if mixer_weights not in WEIGHT_FORMATS:
+        raise ValueError(f"mixer_weights={mixer_weights!r}: expected one of {WEIGHT_FORMATS}")
+    if mixer_weights != "bf16" and not has_mamba2_mixers(cfg):
+        raise NotImplementedError(f'mixer_weights="{mixer_weights}" quantises the Mamba2 mixers\' projections; '
+                                  "this config's backbone has none")
+
+
 def make_engine(cfg: ZonosConfig, device="cuda", max_slots: int = 1, max_seqlen: int = 2048,
-                max_prefill: int = 512, weights: str = "bf16") -> HipEngine:
+                max_prefill: int = 512, weights: str = "bf16", mixer_weights: str = "bf16") -> HipEngine:
     """The engine for a config's backbone: HipEngine (transformer) or HybridEngine (Mamba2 + MHA)."""
     check_weights(weights, bool(cfg.backbone.ssm_cfg))
+    check_mixer_weights(mixer_weights, cfg)
     if cfg.backbone.ssm_cfg:
         from .hybrid import HybridEngine
-        return HybridEngine(cfg, device, max_slots, max_seqlen, max_prefill)
+        return HybridEngine(cfg, device, max_slots, max_seqlen, max_prefill, mixer_weights)
     return HipEngine(cfg, device, max_slots, max_seqlen, max_prefill, weights)

@@ -28,9 +28,9 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, quant
 from .config import EMB_VOCAB, HEAD_VOCAB, N_CODEBOOKS, ROPE_TABLE_LEN
-from .engine import HEADS_N, HEADS_N_PAD, HipEngine
+from .engine import HEADS_N, HEADS_N_PAD, HipEngine, check_mixer_weights
 
 
 def rope_table_neox(hd: int, n: int = ROPE_TABLE_LEN) -> torch.Tensor:
@@ -56,8 +56,16 @@ class HybridEngine(HipEngine):
     # 5p): the pass beats the loop of prefill() from 2 utterances on, so there is no threshold below which it loops.
     prefill_batch = True
 
-    def __init__(self, cfg, device="cuda", max_slots: int = 1, max_seqlen: int = 2048, max_prefill: int = 512):
+    def __init__(self, cfg, device="cuda", max_slots: int = 1, max_seqlen: int = 2048, max_prefill: int = 512,
+                 mixer_weights: str = "bf16"):
         bb = cfg.backbone
+        check_mixer_weights(mixer_weights, cfg)
+        # "bf16", or "fp8": mixer.in_proj / mixer.out_proj of every Mamba2 layer as E4M3 bytes with one power-of-two
+        # exponent per output row (quant.py); every other tensor (the MHA layers' projections, heads, embeddings,
+        # conv1d, norms, dt_bias, A, D, MLPs) stays bf16. Decode reads the bytes (the ADDLN / GRMS / plain GEMVs and
+        # zmi_mamba_block); a prefill pass expands a layer's two projections into bf16 scratch (zmi_unpack_fp8) and
+        # runs the bf16 forms. Either way: exactly the bf16 engine on dequantized_state_dict_overrides().
+        self.mixer_weights = mixer_weights
         if bb.rms_norm or bb.residual_in_fp32:
             raise NotImplementedError("hybrid blocks are built for LayerNorm with bf16 residuals (Zonos-v0.1-hybrid)")
         self.md = bb.mamba2_dims()
@@ -127,11 +135,49 @@ class HybridEngine(HipEngine):
             ws = int(self.lib.zmi_mamba2_scan_ws_bytes(P2, md["d_ssm"], md["nheads"]))
             self.scan_ws = z(ws, dt=torch.uint8)  # zmi_mamba2_scan_seqs: conv output, dt, dA of the prefill rows
             self.rope = rope_table_neox(self.hd).to(dev)
+            # fp8 mixers: one layer's in_proj and out_proj expanded to bf16 (layout M8) for a prefill pass
+            self.mix_scratch = None
+            if self.mixer_weights == "fp8":
+                self.mix_scratch = (torch.empty(md["d_in_proj"] * self.d, dtype=torch.bfloat16, device=dev),
+                                    torch.empty(self.d * md["d_ssm"], dtype=torch.bfloat16, device=dev))
         self.stream.synchronize()
 
     # ------------------------------------------------------------------ weights
-    def load_state_dict(self, sd: dict):
-        """mamba-ssm parameter names (Block norm / mixer / norm2 / mlp; Mamba2, MHA, GatedMLP)."""
+    def _pack_mixer(self, w: torch.Tensor, n_pad: int) -> torch.Tensor:
+        """A Mamba2 projection in the engine's mixer format. bf16: _pack. fp8: ONE uint8 tensor of n_pad * k E4M3
+        bytes in layout M8F8 followed by the n_pad int8 exponents (as HipEngine._pack_mlp); _gemv takes the format
+        and the exponents' address from it."""
+        if self.mixer_weights != "fp8":
+            return self._pack(w, n_pad)
+        q, e = quant.quantize_fp8(w.to(self.dev, torch.bfloat16))
+        packed, ep = quant.pack_m8f8(q, e, n_pad)
+        return torch.cat([packed, ep.view(torch.uint8)])
+
+    def dequantized_state_dict_overrides(self) -> dict:
+        """{state_dict name: bf16 [n][k]} of every quantised tensor (the Mamba2 layers' mixer.in_proj / out_proj),
+        dequantised: a bf16 engine loaded with the same state dict and these in place of the originals computes
+        exactly what this engine computes. Empty for bf16."""
+        out = {}
+        if self.mixer_weights == "fp8":
+            md = self.md
+            with torch.cuda.stream(self.stream):
+                for i, lw in enumerate(self.w["layers"]):
+                    if lw["kind"] != "mamba":
+                        continue
+                    for key, name, n, k in (("in_proj", "in_proj", md["d_in_proj"], self.d),
+                                            ("out", "out_proj", self.d, md["d_ssm"])):
+                        t = lw[key]
+                        q, e = quant.unpack_m8f8(t[: n * k], t[n * k:].view(torch.int8), n, k)
+                        out[f"backbone.layers.{i}.mixer.{name}.weight"] = quant.dequantize_fp8(q, e)
+            self.stream.synchronize()
+        return out
+
+    def load_state_dict(self, sd: dict, consume: bool = False):
+        """mamba-ssm parameter names (Block norm / mixer / norm2 / mlp; Mamba2, MHA, GatedMLP). With
+        mixer_weights="fp8" the Mamba2 projections are quantised and packed one at a time, so the engine holds the bf16
+        form of one projection beside the fp8 copies, never of all of them; consume=True also drops each of them from
+        `sd` once it is packed (a caller that owns the dict, as init_synthetic does)."""
+        take = sd.pop if consume else sd.__getitem__
         bf = lambda t: t.to(self.dev, torch.bfloat16).contiguous()  # noqa: E731
         f32 = lambda t: t.to(self.dev, torch.bfloat16).float().contiguous()  # noqa: E731  (bf16 model params)
         md, hd = self.md, self.hd
@@ -155,14 +201,14 @@ class HybridEngine(HipEngine):
                     ff = self.F
                 else:
                     lw.update(kind="mamba", st=i - sum(1 for j in self.attn_idx if j < i),
-                              in_proj=self._pack(sd[p + "mixer.in_proj.weight"], md["d_in_proj"]),
+                              in_proj=self._pack_mixer(take(p + "mixer.in_proj.weight"), md["d_in_proj"]),
                               conv_w=bf(sd[p + "mixer.conv1d.weight"]).reshape(md["conv_dim"], md["d_conv"]).contiguous(),
                               conv_b=bf(sd[p + "mixer.conv1d.bias"]),
                               dt_bias=f32(sd[p + "mixer.dt_bias"]),
                               A=(-torch.exp(f32(sd[p + "mixer.A_log"]))).contiguous(),
                               D=f32(sd[p + "mixer.D"]),
                               norm_w=bf(sd[p + "mixer.norm.weight"]),
-                              out=self._pack(sd[p + "mixer.out_proj.weight"], self.d))
+                              out=self._pack_mixer(take(p + "mixer.out_proj.weight"), self.d))
                     ff = self.Fm
                 if ff:
                     lw.update(ff=ff, ln2_w=bf(sd[p + "norm2.weight"]), ln2_b=bf(sd[p + "norm2.bias"]),
@@ -180,6 +226,21 @@ class HybridEngine(HipEngine):
         self.stream.synchronize()
         self.w = w
         self._build_plan()
+
+    def init_synthetic(self, seed: int = 0, zero_eos: bool = False, eos_row_scale: float | None = None):
+        sd = self.synthetic_state_dict(seed, zero_eos, eos_row_scale)
+        if self.mixer_weights == "fp8":
+            self.load_state_dict(sd, consume=True)
+        else:
+            self.load_state_dict(sd)
+
+    def _expand_mixer(self, w: torch.Tensor, n: int, k: int, out: torch.Tensor):
+        """The launch that expands an fp8 projection (n * k M8F8 bytes, then n exponents) into bf16 layout M8."""
+        lib, s, wp, ep, op = self.lib, self.sptr, w.data_ptr(), w.data_ptr() + n * k, out.data_ptr()
+
+        def run():
+            _lib.check(lib.zmi_unpack_fp8(wp, ep, n, k, op, s), "unpack_fp8")
+        return run
 
     def _reset_granules(self, slot: int):
         super()._reset_granules(slot)
@@ -228,7 +289,7 @@ class HybridEngine(HipEngine):
         ia.row_pos = sa.row_pos  # the in_proj epilogue tags its granules with the row's position + 1
         pf = _lib.Prefetch()
         if out_w is not None and self.prefetch_blocks > 0:  # out_proj's weights into the Infinity Cache
-            pf.ptr[0], pf.bytes[0] = out_w.data_ptr(), out_w.numel() * 2
+            pf.ptr[0], pf.bytes[0] = out_w.data_ptr(), out_w.numel() * out_w.element_size()
             pf.sink, pf.blocks = self.blk_err[2:].data_ptr(), self.prefetch_blocks
 
         def run():
@@ -262,7 +323,17 @@ class HybridEngine(HipEngine):
                                                                            table)))
             items.append(("gemv", self._gemv(lw["out"], attn, m, d, qd, _lib.EPI_STORE, hid, d)))
         else:
-            items.append(("gemv", self._gemv(lw["in_proj"], nrm, m, md["d_in_proj"], d, _lib.EPI_STORE, zx,
+            w_in, w_out = lw["in_proj"], lw["out"]
+            if w_in.dtype == torch.uint8:
+                # fp8 mixers: a pass is many rows per weight, and its many-row, split-K and tile forms read bf16. So the
+                # layer's two projections are expanded into the scratch first (stream order lets the next layer reuse
+                # it) and the launches below are the bf16 engine's. There is no plain fp8 in_proj launch.
+                if scan is None:
+                    raise RuntimeError("fp8 mixers: the plain in_proj launch is not built (decode runs _plan)")
+                items.append(("call", self._expand_mixer(w_in, md["d_in_proj"], d, self.mix_scratch[0])))
+                items.append(("call", self._expand_mixer(w_out, d, md["d_ssm"], self.mix_scratch[1])))
+                w_in, w_out = self.mix_scratch
+            items.append(("gemv", self._gemv(w_in, nrm, m, md["d_in_proj"], d, _lib.EPI_STORE, zx,
                                              md["d_in_proj"])))
             if scan is None:
                 items.append(("call", self._call_step(self._mamba_args(lw, zx, yb, m, row_pos, None))))
@@ -275,7 +346,7 @@ class HybridEngine(HipEngine):
                 items.append(("call", lambda a=a: _lib.check(fn(
                     ctypes.byref(a), sp, len(sa), sa.ctypes.data, wp, wn, s), name)))
             items.append(("call", self._gnorm(lw, yb, zx, yn, m)))
-            items.append(("gemv", self._gemv(lw["out"], yn, m, d, md["d_ssm"], _lib.EPI_STORE, hid, d)))
+            items.append(("gemv", self._gemv(w_out, yn, m, d, md["d_ssm"], _lib.EPI_STORE, hid, d)))
         if lw.get("ff"):
             ff = lw["ff"]
             items.append(("call", self._addln(hid, x, (lw["ln2_w"], lw["ln2_b"]), nrm, m)))
@@ -326,7 +397,7 @@ class HybridEngine(HipEngine):
                     if self._use_attn_block(rows, form):
                         pf = _lib.Prefetch()
                         if self.prefetch_blocks > 0 and not oproj:  # out_proj's weights into the Infinity Cache meanwhile
-                            pf.ptr[0], pf.bytes[0] = lw["out"].data_ptr(), lw["out"].numel() * 2
+                            pf.ptr[0], pf.bytes[0] = lw["out"].data_ptr(), lw["out"].numel() * lw["out"].element_size()
                             pf.sink, pf.blocks = self.blk_err[2:].data_ptr(), self.prefetch_blocks
                         o_item = self._gemv(lw["out"], self.attn, rows, d, qd, _lib.EPI_STORE, self.hid, d)
                         plan.append(("attnblk", (qkv[1][0], j, pf, self._block_slices(form)) +

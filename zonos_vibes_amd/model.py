@@ -40,15 +40,20 @@ def _draw_seed() -> int:
 
 class Zonos:
     def __init__(self, config: ZonosConfig, device="cuda", max_slots: int = 1, max_seqlen: int = 2048,
-                 max_prefill: int = 512, autoencoder: DACAutoencoder | None = None, weights: str = "bf16"):
+                 max_prefill: int = 512, autoencoder: DACAutoencoder | None = None, weights: str = "bf16",
+                 mixer_weights: str = "bf16"):
         """weights: "bf16", or "fp8" for weight-only E4M3 MLP projections (transformer backbones; quant.py): the
-        decode step then streams 0.6 of the bytes and computes exactly the bf16 model on the dequantised weights."""
+        decode step then streams 0.6 of the bytes and computes exactly the bf16 model on the dequantised weights.
+        mixer_weights: "bf16", or "fp8" for the same format on the Mamba2 mixers' in_proj / out_proj (hybrid
+        backbones): half the bytes of those projections per decode step and per replica, again exactly the bf16
+        model on the dequantised weights."""
         self.config = config
         self.eos_token_id = config.eos_token_id
         self.masked_token_id = config.masked_token_id
         self._device = torch.device(device)
         self.weights = weights
-        self.engine = make_engine(config, device, max_slots, max_seqlen, max_prefill, weights)
+        self.mixer_weights = mixer_weights
+        self.engine = make_engine(config, device, max_slots, max_seqlen, max_prefill, weights, mixer_weights)
         self.autoencoder = autoencoder if autoencoder is not None else DACAutoencoder(device)
         pcc = config.prefix_conditioner
         self.prefix_conditioner = (PrefixConditioner(pcc.conditioners, config.backbone.d_model, device, pcc.projection)
@@ -114,7 +119,7 @@ class Zonos:
         if slots > e.S or seqlen > e.smax or prefill > e.max_prefill:
             w = e.w
             self.engine = make_engine(self.config, self._device, max(slots, e.S), max(seqlen, e.smax),
-                                      max(prefill, e.max_prefill), self.weights)
+                                      max(prefill, e.max_prefill), self.weights, self.mixer_weights)
             self.engine.w = w
             self.engine._build_plan()
 
@@ -575,7 +580,7 @@ class Zonos:
         bb = self.config.backbone
         kind = "hybrid" if bb.is_hybrid else "transformer"
         return (f"Zonos(hip {kind}, d={bb.d_model}, layers={bb.n_layer}, heads={bb.num_heads}/{bb.num_heads_kv}, "
-                f"weights={self.weights})")
+                f"weights={self.weights}" + (f", mixer_weights={self.mixer_weights})" if bb.is_hybrid else ")"))
 
 
 __all__ = ["Zonos", "DACAutoencoder", "N_CODEBOOKS"]
