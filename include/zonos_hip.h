@@ -291,14 +291,18 @@ int zmi_sample_logits(const float* logits, const int* generated, int gen_len, in
 int zmi_apply_delay_pattern(const int64_t* codes, int64_t* out, int batch, int T, int64_t mask_token, void* stream);
 int zmi_revert_delay_pattern(const int64_t* codes, int64_t* out, int batch, int T, void* stream);
 /* x[2s], x[2s+1] = sum_k emb_k[delayed[s][k][offset[s]]]  (model.py:97-98,142; single layout: x[s]) and the
- * per-row (kv row, position) tables of the step (-1 position for inactive slots). */
+ * per-row (kv row, position) tables of the step (-1 position for inactive slots). Refused before any launch:
+ * d not a positive multiple of 8, NULL emb or x. */
 int zmi_embed_step(const ZmiSlots* slots, const void* emb, int d, void* x, int* row_kv, int* row_pos,
                    void* stream);
-/* prefill embedding rows: x[s] = sum_k emb_k[codes[k][s]] for s < n (model.py:195) */
+/* prefill embedding rows: x[s] = sum_k emb_k[codes[k][s]] for s < n (model.py:195). Refused before any launch:
+ * n <= 0, d not a positive multiple of 8, ldx < d, ld_codes < n, NULL codes, emb or x. */
 int zmi_embed_codes(const int* codes, int ld_codes, int n, const void* emb, int d, void* x, int ldx, void* stream);
-/* delayed[slot] = apply_delay_pattern(prefix codes | -1)    (codebook_pattern.py:5-7)      */
+/* delayed[slot] = apply_delay_pattern(prefix codes | -1)    (codebook_pattern.py:5-7). Refused before any launch:
+ * slot out of range, total_len > tcap, a negative prefix_len or total_len, prefix_len > 0 with a NULL prefix. */
 int zmi_delay_init(const ZmiSlots* slots, int slot, const int* prefix, int prefix_len, int total_len, void* stream);
-/* out[9][T] int64 = revert_delay_pattern(delayed[slot]) with >=1024 -> 0 (model.py:309-311) */
+/* out[9][T] int64 = revert_delay_pattern(delayed[slot]) with >=1024 -> 0 (model.py:309-311). Refused before any
+ * launch: slot out of range, t_out + 9 > tcap, NULL out with t_out > 0. */
 int zmi_delay_revert(const ZmiSlots* slots, int slot, int64_t* out, int t_out, void* stream);
 /* frames t0 .. t0 + n - 1 of that result, out[9][n] int64: out[k][i] = delayed[slot][k][t0 + i + k + 1] with
  * >=1024 -> 0 (codebook_pattern.py:9-12, model.py:309-311). Frames below offset - 9 of a running slot are final,
@@ -514,7 +518,8 @@ typedef struct ZmiCondRow {
   int index;  /* EMBED row                                                                       */
   int x_off;  /* offset of this row's inputs in x (FOURIER / LINEAR / PASSTHROUGH)               */
 } ZmiCondRow;
-/* out[r][0..d) = LayerNorm(row r) for r < n_rows; params / rows / x are device arrays. */
+/* out[r][0..d) = LayerNorm(row r) for r < n_rows; params / rows / x are device arrays. Refused before any launch:
+ * d odd, <= 0 or > 4096, a negative n_rows, and with n_rows > 0 a NULL params, rows, x, ln_w, ln_b or out. */
 int zmi_prefix_condition(const ZmiCondParam* params, const ZmiCondRow* rows, int n_rows, const float* x, int d,
                          const void* ln_w, const void* ln_b, float eps, void* out, void* stream);
 

@@ -124,7 +124,10 @@ __global__ __launch_bounds__(NT) void cond_kernel(const ZmiCondParam* __restrict
 extern "C" int zmi_prefix_condition(const ZmiCondParam* params, const ZmiCondRow* rows, int n_rows, const float* x,
                                     int d, const void* ln_w, const void* ln_b, float eps, void* out, void* stream) {
   if (d <= 0 || d > MAXD || (d & 1)) return zmi_fail_msg("prefix_condition: d must be even and <= 4096");
-  if (n_rows <= 0) return 0;
+  if (n_rows < 0) return zmi_fail_msg("prefix_condition: negative n_rows");
+  if (n_rows == 0) return 0;
+  if (!params || !rows || !x || !ln_w || !ln_b || !out)
+    return zmi_fail_msg("prefix_condition: params, rows, x, ln_w, ln_b and out must not be NULL");
   hipLaunchKernelGGL(cond_kernel, dim3(n_rows), dim3(NT), 0, (hipStream_t)stream, params, rows, x, d,
                      (const bf16_t*)ln_w, (const bf16_t*)ln_b, eps, (bf16_t*)out);
   ZMI_CHECK(hipGetLastError());

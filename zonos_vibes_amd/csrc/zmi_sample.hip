@@ -776,9 +776,10 @@ extern "C" int zmi_sample_step_greedy(const ZmiSlots* slots, const float* logits
 
 extern "C" int zmi_embed_step(const ZmiSlots* slots, const void* emb, int d, void* x, int* row_kv, int* row_pos,
                               void* stream) {
-  if (d % 8) return zmi_fail_msg("embed: d % 8");
+  if (d <= 0 || d % 8) return zmi_fail_msg("embed_step: d must be a positive multiple of 8");
+  if (!emb || !x) return zmi_fail_msg("embed_step: emb and x must not be NULL");
   const int rps = slots_layout(slots);
-  if (rps < 0) return zmi_fail_msg("embed: rows_per_slot must be 0 or 2 (paired) or 1 (single)");
+  if (rps < 0) return zmi_fail_msg("embed_step: rows_per_slot must be 0 or 2 (paired) or 1 (single)");
   if (rps == 2)
     hipLaunchKernelGGL(embed_step_kernel<2>, dim3(slots->n_slots), dim3(256), 0, (hipStream_t)stream, *slots,
                        (const bf16_t*)emb, d, (bf16_t*)x, row_kv, row_pos);
@@ -791,7 +792,9 @@ extern "C" int zmi_embed_step(const ZmiSlots* slots, const void* emb, int d, voi
 
 extern "C" int zmi_embed_codes(const int* codes, int ld_codes, int n, const void* emb, int d, void* x, int ldx,
                                void* stream) {
-  if (d % 8 || n <= 0) return zmi_fail_msg("embed_codes: bad shape");
+  if (d <= 0 || d % 8 || n <= 0) return zmi_fail_msg("embed_codes: bad shape");
+  if (ldx < d || ld_codes < n) return zmi_fail_msg("embed_codes: ldx < d or ld_codes < n");
+  if (!codes || !emb || !x) return zmi_fail_msg("embed_codes: codes, emb and x must not be NULL");
   hipLaunchKernelGGL(embed_codes_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, codes, ld_codes,
                      (const bf16_t*)emb, d, (bf16_t*)x, ldx);
   ZMI_CHECK(hipGetLastError());
@@ -801,6 +804,8 @@ extern "C" int zmi_embed_codes(const int* codes, int ld_codes, int n, const void
 extern "C" int zmi_delay_init(const ZmiSlots* slots, int slot, const int* prefix, int prefix_len, int total_len,
                               void* stream) {
   if (total_len > slots->tcap || slot < 0 || slot >= slots->n_slots) return zmi_fail_msg("delay_init: bounds");
+  if (prefix_len < 0 || total_len < 0) return zmi_fail_msg("delay_init: negative prefix_len or total_len");
+  if (prefix_len > 0 && !prefix) return zmi_fail_msg("delay_init: prefix_len > 0 with a NULL prefix");
   hipLaunchKernelGGL(delay_init_kernel, dim3((slots->tcap + 255) / 256, ZMI_NCB), dim3(256), 0,
                      (hipStream_t)stream, *slots, slot, prefix, prefix_len, total_len);
   ZMI_CHECK(hipGetLastError());
@@ -808,8 +813,10 @@ extern "C" int zmi_delay_init(const ZmiSlots* slots, int slot, const int* prefix
 }
 
 extern "C" int zmi_delay_revert(const ZmiSlots* slots, int slot, int64_t* out, int t_out, void* stream) {
+  if (slot < 0 || slot >= slots->n_slots) return zmi_fail_msg("delay_revert: slot");
   if (t_out <= 0) return 0;
   if (t_out + ZMI_NCB > slots->tcap) return zmi_fail_msg("delay_revert: bounds");
+  if (!out) return zmi_fail_msg("delay_revert: out must not be NULL");
   hipLaunchKernelGGL(delay_revert_kernel, dim3((t_out + 255) / 256, ZMI_NCB), dim3(256), 0, (hipStream_t)stream,
                      *slots, slot, out, t_out);
   ZMI_CHECK(hipGetLastError());
