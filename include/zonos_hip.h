@@ -57,8 +57,13 @@ enum { ZMI_PRO_AUTO = 0, ZMI_PRO_ADDLN = 2, ZMI_PRO_GRMS = 3, ZMI_PRO_GRMS_G = 4
  *             under GRMS / GRMS_G (K 1024 / 4096, M <= 4) or plain at K 1024 / 4096 (any M). A plain STORE launch at
  *             K 512 / 2048 / 8192, the QKV and LOGITS epilogues and the LayerNorm prologue with STORE are refused;
  *           - zmi_mamba_block / zmi_mamba_block_pf (the in_proj role; a kernel of its own name).
- *         The split-K GEMM, the many-row form and zmi_attn_block read bf16 only: a prefill expands a projection with
- *         zmi_unpack_fp8 and runs the bf16 forms on the result. */
+ *         The MLP launches take every launch form the bf16 ones do: over more than 16 plain rows at K = 2048 (fc1) the
+ *         many-row form (zmi_gemv_form reports ZMI_FORM_ROWS / ZMI_FORM_ROWS_DENSE while ZMI_OPT_FP8_ROWS is set), its
+ *         bytes expanded to bf16 registers once per workgroup; fc2 (K = 8192, RESIDUAL) also as a split-K GEMM through
+ *         entry points of its own, zmi_gemv_splitk_f8 / zmi_gemv_splitk_f8_ln. Every form gives the same bits.
+ *         zmi_gemv_splitk / zmi_gemv_splitk_ln and zmi_attn_block read bf16 only, and no many-row form reads the
+ *         Mamba2 mixers' fp8 projections: a prefill expands such a projection with zmi_unpack_fp8 and runs the bf16
+ *         forms on the result. */
 enum { ZMI_WFMT_BF16 = 0, ZMI_WFMT_FP8 = 1 };
 
 typedef struct ZmiGemvArgs {
@@ -123,6 +128,14 @@ int zmi_gemv_splitk(const ZmiGemvArgs* args, int epi, float* part, int64_t part_
 int zmi_gemv_splitk_ln(const ZmiGemvArgs* args, int epi, float* part, int64_t part_floats, const void* ln_w,
                        const void* ln_b, float eps, void* xn, int ldxn, void* stream);
 int64_t zmi_gemv_splitk_floats(int M, int N);
+/* The split-K GEMM over FP8 weights, for fc2: w_fmt == ZMI_WFMT_FP8 with w_exp (8-byte aligned), K = 8192 and
+ * EPI_RESIDUAL only; the other conditions are zmi_gemv_splitk_ln's, and everything else is refused before any launch
+ * with `out` and `part` untouched. `part` holds the unscaled segment sums; the reduce adds the 8 segments in order,
+ * multiplies by the column's 2^w_exp[n] and applies the residual epilogue (and the LayerNorm): the bits of
+ * zmi_gemv_launch over the same FP8 weights, hence of the BF16 launch on the dequantised ones. */
+int zmi_gemv_splitk_f8(const ZmiGemvArgs* args, int epi, float* part, int64_t part_floats, void* stream);
+int zmi_gemv_splitk_f8_ln(const ZmiGemvArgs* args, int epi, float* part, int64_t part_floats, const void* ln_w,
+                          const void* ln_b, float eps, void* xn, int ldxn, void* stream);
 /* out[r] = LayerNorm(x[r]) bf16, r < m (nn.LayerNorm, _torch.py:62: norm_f for the backbone plugin),
  * with the GEMV LayerNorm prologue's arithmetic; k in {512, 1024, 2048, 4096}. */
 int zmi_layernorm_rows(const void* x, int ldx, int m, int k, const void* w, const void* b, float eps, void* out,
@@ -627,7 +640,9 @@ const char* zmi_last_error(void);
  * [tap][ci / 32][co][32] (zmi_dac_conv / conv_t / conv_out) and the round-5 ZMI_OPT_GEMM_ROWS bits; 5 =
  * ZMI_OPT_XC_HANDOFF and zmi_xcd_dealing; 6 = ZMI_PRO_GRMS_G and ZmiMamba2Args.gz_g; 7 = the zmi_dac_*_lanes entry points.
  * (zmi_unpack_fp8 and the FP8 forms of the Mamba2 projections were added at version 10: no layout, struct or option
- * changed meaning, and every launch a version-10 caller could make gives what it gave.) Check it before packing weights (zonos_vibes_amd/_lib.py refuses a library
+ * changed meaning, and every launch a version-10 caller could make gives what it gave. Likewise zmi_gemv_splitk_f8,
+ * zmi_gemv_splitk_f8_ln and ZMI_OPT_FP8_ROWS, added at version 10: FP8 launches over many rows take another form, and
+ * give the same bits.) Check it before packing weights (zonos_vibes_amd/_lib.py refuses a library
  * whose version differs). */
 int zmi_version(void);
 /* 1 if this device deals a launch's workgroups round-robin over its XCDs (blocks b and b + 8 on one XCD, 8
@@ -670,11 +685,14 @@ int zmi_xcd_dealing(void* stream);
  *   ZMI_OPT_SPLITK_WGS (default 256): zmi_gemv_splitk splits the rows into groups of 16-row tiles until its grid
  *          has about this many workgroups (each row group re-reads its segment's weights); 0 = one row group.
  *   ZMI_OPT_SPLITK_STAGE (default 1): zmi_gemv_splitk stages 2 (K segment 1024) or 4 (512) 16-row tiles per LDS
- *          buffer, so twice the activation bytes are in flight per CU (~132 KB of LDS); 0 = one tile per buffer. */
+ *          buffer, so twice the activation bytes are in flight per CU (~132 KB of LDS); 0 = one tile per buffer.
+ *          (ZMI_OPT_GEMM_ROWS bit 1, ZMI_OPT_SPLITK_WGS and ZMI_OPT_SPLITK_STAGE shape zmi_gemv_splitk_f8 alike.)
+ *   ZMI_OPT_FP8_ROWS (default 1): zmi_gemv_launch over FP8 weights takes the many-row form wherever the same launch
+ *          over bf16 weights does (ZMI_OPT_GEMM_ROWS picks M8 or dense pairs); 0 = gemv_body's tile loop for every M. */
 enum { ZMI_OPT_GEMV_SPREAD = 0, ZMI_OPT_GEMM_ROWS = 1, ZMI_OPT_XC_HANDOFF = 2, /* 3..9 reserved */
        ZMI_OPT_DAC_WIDE = 10, ZMI_OPT_DAC_WIDE_MIN = 11, ZMI_OPT_ATTNBLK_SPREAD = 12, ZMI_OPT_DAC_STAGE = 13,
        ZMI_OPT_DAC_STAGE_MIN = 14, ZMI_OPT_SCAN_PQ = 15, ZMI_OPT_SPLITK_WGS = 16, ZMI_OPT_SPLITK_STAGE = 17,
-       ZMI_OPT_COUNT = 18 };
+       ZMI_OPT_FP8_ROWS = 18, ZMI_OPT_COUNT = 19 };
 int zmi_set_option(int which, int value);
 int zmi_get_option(int which);
 

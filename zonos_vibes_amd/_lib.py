@@ -29,6 +29,7 @@ OPT_DAC_STAGE_MIN = 14
 OPT_SCAN_PQ = 15
 OPT_SPLITK_WGS = 16
 OPT_SPLITK_STAGE = 17
+OPT_FP8_ROWS = 18  # 1: fp8 GEMV launches over many rows take the many-row form where bf16 ones do; 0: the tile loop
 ATTNBLK_SELF, ATTNBLK_SPLIT = 256, 512  # zmi_attn_block slices flags: self-scoring / chunk-split forms
 PACK_IDENTITY, PACK_SWIGLU = 0, 1
 PRO_AUTO, PRO_ADDLN, PRO_GRMS, PRO_GRMS_G = 0, 2, 3, 4
@@ -143,6 +144,10 @@ _SIGS = {
     "zmi_gemv_splitk_floats": (c_int64, [c_int, c_int]),
     "zmi_gemv_splitk_ln": (c_int, [ctypes.POINTER(GemvArgs), c_int, c_void_p, c_int64, c_void_p, c_void_p, c_float,
                                    c_void_p, c_int, c_void_p]),
+    # fc2 over fp8 weights (K = 8192, EPI_RESIDUAL): the same split-K GEMM on M8F8 bytes
+    "zmi_gemv_splitk_f8": (c_int, [ctypes.POINTER(GemvArgs), c_int, c_void_p, c_int64, c_void_p]),
+    "zmi_gemv_splitk_f8_ln": (c_int, [ctypes.POINTER(GemvArgs), c_int, c_void_p, c_int64, c_void_p, c_void_p, c_float,
+                                      c_void_p, c_int, c_void_p]),
     "zmi_attn_block_pf": (c_int, [ctypes.POINTER(GemvArgs), c_void_p, c_void_p, c_void_p, c_int, c_int,
                                   ctypes.POINTER(Prefetch), c_void_p]),
     "zmi_attn_block_oproj": (c_int, [ctypes.POINTER(GemvArgs), ctypes.POINTER(GemvArgs), c_void_p, c_void_p, c_void_p,

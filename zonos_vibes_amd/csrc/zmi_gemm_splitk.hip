@@ -39,9 +39,14 @@ constexpr int DNWV = 4, DNT = DNWV * 64;
 // Grid: (row group, K segment, column block), column blocks fastest. A row group is `rpg` consecutive 16-row tiles
 // (several row groups re-read the segment's weights, from L2 when they run together; speed only: a row's sums
 // do not depend on the grouping).
-template <int K, bool DN, int RTS>
+// FMT fp8 (layout M8F8, fc2 only): half the weight loads, expanded once into the bf16 registers (expand_fp8) before the
+// stage loop, which is the bf16 one; `part` then holds the unscaled sums of the E4M3 values, and the fp8 reduce scales
+// the finished column sum by its 2^e.
+template <int K, bool DN, int RTS, int FMT = ZMI_WFMT_BF16>
 __global__ __launch_bounds__(DN ? DNT : NT) void splitk_kernel(const ZmiGemvArgs a, float* part, int n_cb, int rpg) {
   using S = Shape<K>;
+  constexpr bool F8 = FMT == ZMI_WFMT_FP8;
+  static_assert(FMT == ZMI_WFMT_BF16 || (F8 && K == 8192), "fp8 weights: fc2");
   using namespace zmi_gemv;  // dma_piece and the row arithmetic (zmi_gemv_row.h)
   constexpr int NSEG = S::NSEG, KS = S::KS, NL = S::NL, KC = S::KC, SROW = S::SROW, TILE_BYTES = S::TILE_BYTES;
   constexpr int NW = DN ? DNWV : NWV;  // waves
@@ -73,12 +78,23 @@ __global__ __launch_bounds__(DN ? DNT : NT) void splitk_kernel(const ZmiGemvArgs
   // (DN: the descriptor starts at the column block's first group, the lane's group g at an offset from it)
   constexpr int NH = DN ? 2 : 1;
   u32x4_t wf[NH][NL];
-  if constexpr (DN)
+  if constexpr (F8) {
+    u32x4_t raw[NH][NL / 2];
+    if constexpr (DN)
+      load_weights_dn_f8<NL, 2>(reinterpret_cast<const char*>(a.W) + ((size_t)cb * NWV * KC + seg * NL) * 512,
+                                NWV * KC * 512, (g - cb * NWV) * KC * 512, lane, raw);
+    else
+      load_weights_m8<NL / 2, 2>(reinterpret_cast<const char*>(a.W) + ((size_t)g * KC + seg * NL) * 512, NL * 512, lane,
+                                 raw[0]);
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NH * NL / 2) : "memory");  // the first stage's pieces (issued before)
+#pragma unroll
+    for (int h = 0; h < NH; ++h) expand_fp8<NL>(raw[h], wf[h]);  // (the compiler's own wait for the weights)
+  } else if constexpr (DN)
     load_weights_dn<NL, 2>(reinterpret_cast<const char*>(a.W) + ((size_t)cb * NWV * KC + seg * NL) * 1024, NWV * KC * 1024,
                            (g - cb * NWV) * KC * 1024, lane, wf);
   else
     load_weights_m8<NL, 2>(reinterpret_cast<const char*>(a.W) + ((size_t)g * KC + seg * NL) * 1024, NL * 1024, lane, wf[0]);
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NH * NL) : "memory");  // the first stage's pieces (issued before)
+  if constexpr (!F8) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NH * NL) : "memory");  // the first stage's pieces (issued before)
   for (int st = 0; st < n_st; ++st) {
     __syncthreads();  // stage st landed for every wave's pieces; the other buffer is free
     if (st + 1 < n_st) stage(st + 1, (st + 1) & 1);
@@ -108,14 +124,17 @@ __global__ __launch_bounds__(DN ? DNT : NT) void splitk_kernel(const ZmiGemvArgs
 
 // x[m][n] = bf16(x + bf16(sum over the segments in order)), the GEMV's EPI_RESIDUAL epilogue; RES false: out = bf16(sum),
 // its EPI_STORE epilogue
-template <int NSEG, bool RES>
-__global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* part, int M, int N, bf16_t* out, int ldo) {
+// F8: the finished sum times the column's 2^w_exp[n] before any rounding (ColSum's order)
+template <int NSEG, bool RES, bool F8 = false>
+__global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* part, int M, int N, bf16_t* out, int ldo,
+                                                            const signed char* w_exp = nullptr) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= (size_t)M * N) return;
   const size_t m = i / N, n = i - m * N;
   float v = part[i];
 #pragma unroll
   for (int s = 1; s < NSEG; ++s) v += part[(size_t)s * M * N + i];
+  if constexpr (F8) v *= __uint_as_float((uint32_t)((int)w_exp[n] + 127) << 23);
   bf16_t* o = out + m * ldo + n;
   if (RES)
     *o = (bf16_t)f2bf(bf2f(*o) + bfround(v));
@@ -127,10 +146,10 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* part, i
 // op's prologue, zmi_rownorm.h's LayerNorm as in zmi_layernorm_rows: part q = wave q, one chunk per lane, two
 // passes): one 4-wave workgroup per row, so the next layer's LayerNorm pre-pass launch
 // is not needed.
-template <int NSEG>
+template <int NSEG, bool F8 = false>
 __global__ __launch_bounds__(256) void splitk_reduce_ln_kernel(const float* part, int M, bf16_t* out, int ldo,
                                                                const bf16_t* lw, const bf16_t* lb, float eps,
-                                                               bf16_t* xn, int ldn) {
+                                                               bf16_t* xn, int ldn, const signed char* w_exp = nullptr) {
   constexpr int N = 2048, NQ = ln_parts(N);
   static_assert(NQ == 4 && ln_chunks(N) == 1, "one wave per LayerNorm part, one chunk per lane");
   __shared__ float ps[2][NQ];
@@ -148,6 +167,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_ln_kernel(const float* part
   }
   const uint32_t xu[4] = {xv.x, xv.y, xv.z, xv.w};
   uint32_t nu[4];
+  uint2 ex = {0u, 0u};  // F8: the exponents of the lane's 8 columns (one group: e0 is a multiple of 8)
+  if constexpr (F8) ex = *reinterpret_cast<const uint2*>(w_exp + e0);
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     float v0 = j < 2 ? (j == 0 ? pv[0][0].x : pv[0][0].z) : (j == 2 ? pv[0][1].x : pv[0][1].z);
@@ -156,6 +177,10 @@ __global__ __launch_bounds__(256) void splitk_reduce_ln_kernel(const float* part
     for (int s = 1; s < NSEG; ++s) {
       v0 += j < 2 ? (j == 0 ? pv[s][0].x : pv[s][0].z) : (j == 2 ? pv[s][1].x : pv[s][1].z);
       v1 += j < 2 ? (j == 0 ? pv[s][0].y : pv[s][0].w) : (j == 2 ? pv[s][1].y : pv[s][1].w);
+    }
+    if constexpr (F8) {  // the finished sums times their columns' 2^e, before any rounding (ColSum's order)
+      v0 *= zmi_gemv::fp8_col_scale(ex, 2 * j);
+      v1 *= zmi_gemv::fp8_col_scale(ex, 2 * j + 1);
     }
     nu[j] = f2bf(bf2f(xu[j]) + bfround(v0)) | (f2bf(bf2f(xu[j] >> 16) + bfround(v1)) << 16);
   }
@@ -177,10 +202,11 @@ __global__ __launch_bounds__(256) void splitk_reduce_ln_kernel(const float* part
 extern "C" int64_t zmi_gemv_splitk_floats(int M, int N) { return M <= 0 || N <= 0 ? -1 : (int64_t)8 * M * N; }
 
 namespace {
-template <int K>
+template <int K, int FMT = ZMI_WFMT_BF16>
 int launch_splitk(const ZmiGemvArgs& a, int epi, float* part, const void* ln_w, const void* ln_b, float eps, void* xn,
                   int ldxn, hipStream_t s) {
   using S = Shape<K>;
+  constexpr bool F8 = FMT == ZMI_WFMT_FP8;
   const int n_cb = a.N / (8 * NWV);
   // row groups: about ZMI_OPT_SPLITK_WGS workgroups in all (0: one row group)
   const int n_rt = (a.M + RT - 1) / RT, target = zmi_option(ZMI_OPT_SPLITK_WGS);
@@ -190,32 +216,36 @@ int launch_splitk(const ZmiGemvArgs& a, int epi, float* part, const void* ln_w, 
   const size_t lds = 2 * (size_t)(multi ? S::RTS : 1) * S::TILE_BYTES;
   // once per instantiation: allow the stage buffers' dynamic LDS
   static const hipError_t attr[4] = {
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&splitk_kernel<K, false, 1>),
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&splitk_kernel<K, false, 1, FMT>),
                           hipFuncAttributeMaxDynamicSharedMemorySize, 2 * S::TILE_BYTES),
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&splitk_kernel<K, true, 1>),
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&splitk_kernel<K, true, 1, FMT>),
                           hipFuncAttributeMaxDynamicSharedMemorySize, 2 * S::TILE_BYTES),
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&splitk_kernel<K, false, S::RTS>),
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&splitk_kernel<K, false, S::RTS, FMT>),
                           hipFuncAttributeMaxDynamicSharedMemorySize, 2 * S::RTS * S::TILE_BYTES),
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&splitk_kernel<K, true, S::RTS>),
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&splitk_kernel<K, true, S::RTS, FMT>),
                           hipFuncAttributeMaxDynamicSharedMemorySize, 2 * S::RTS * S::TILE_BYTES)};
   for (hipError_t e : attr) ZMI_CHECK(e);
   const dim3 grid(n_cb * S::NSEG * ((n_rt + rpg - 1) / rpg));
   const bool dn = zmi_option(ZMI_OPT_GEMM_ROWS) & 2;
   if (dn && multi)
-    hipLaunchKernelGGL((splitk_kernel<K, true, S::RTS>), grid, dim3(DNT), lds, s, a, part, n_cb, rpg);
+    hipLaunchKernelGGL((splitk_kernel<K, true, S::RTS, FMT>), grid, dim3(DNT), lds, s, a, part, n_cb, rpg);
   else if (dn)
-    hipLaunchKernelGGL((splitk_kernel<K, true, 1>), grid, dim3(DNT), lds, s, a, part, n_cb, rpg);
+    hipLaunchKernelGGL((splitk_kernel<K, true, 1, FMT>), grid, dim3(DNT), lds, s, a, part, n_cb, rpg);
   else if (multi)
-    hipLaunchKernelGGL((splitk_kernel<K, false, S::RTS>), grid, dim3(NT), lds, s, a, part, n_cb, rpg);
+    hipLaunchKernelGGL((splitk_kernel<K, false, S::RTS, FMT>), grid, dim3(NT), lds, s, a, part, n_cb, rpg);
   else
-    hipLaunchKernelGGL((splitk_kernel<K, false, 1>), grid, dim3(NT), lds, s, a, part, n_cb, rpg);
+    hipLaunchKernelGGL((splitk_kernel<K, false, 1, FMT>), grid, dim3(NT), lds, s, a, part, n_cb, rpg);
   ZMI_CHECK(hipGetLastError());
   if (ln_w) {
-    hipLaunchKernelGGL(splitk_reduce_ln_kernel<S::NSEG>, dim3(a.M), dim3(256), 0, s, part, a.M, (bf16_t*)a.out, a.ldo,
-                       (const bf16_t*)ln_w, (const bf16_t*)ln_b, eps, (bf16_t*)xn, ldxn);
+    hipLaunchKernelGGL((splitk_reduce_ln_kernel<S::NSEG, F8>), dim3(a.M), dim3(256), 0, s, part, a.M, (bf16_t*)a.out,
+                       a.ldo, (const bf16_t*)ln_w, (const bf16_t*)ln_b, eps, (bf16_t*)xn, ldxn,
+                       (const signed char*)a.w_exp);
   } else {
     const size_t total = (size_t)a.M * a.N;
-    if (epi == ZMI_EPI_RESIDUAL)
+    if constexpr (F8)  // fc2: EPI_RESIDUAL only (zmi_gemv_splitk_f8_ln)
+      hipLaunchKernelGGL((splitk_reduce_kernel<S::NSEG, true, true>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                         s, part, a.M, a.N, (bf16_t*)a.out, a.ldo, (const signed char*)a.w_exp);
+    else if (epi == ZMI_EPI_RESIDUAL)
       hipLaunchKernelGGL((splitk_reduce_kernel<S::NSEG, true>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s,
                          part, a.M, a.N, (bf16_t*)a.out, a.ldo);
     else
@@ -227,11 +257,9 @@ int launch_splitk(const ZmiGemvArgs& a, int epi, float* part, const void* ln_w, 
 }
 }  // namespace
 
-extern "C" int zmi_gemv_splitk_ln(const ZmiGemvArgs* args, int epi, float* part, int64_t part_floats, const void* ln_w,
-                                  const void* ln_b, float eps, void* xn, int ldxn, void* stream) {
-  const ZmiGemvArgs& a = *args;
-  // before any launch: the kernel would read E4M3 bytes as bf16
-  if (a.w_fmt != ZMI_WFMT_BF16) return zmi_fail_msg("gemv_splitk: bf16 weights only (fp8 weights run zmi_gemv_launch)");
+// the argument checks both weight formats share (0 = accepted; else zmi_last_error is set)
+static int check_splitk(const ZmiGemvArgs& a, int epi, const float* part, int64_t part_floats, const void* ln_w,
+                        const void* ln_b, const void* xn, int ldxn) {
   if (ln_w && (!ln_b || !xn || a.N != 2048 || ldxn < 2048 || ldxn % 8 || a.ldo % 8))
     return zmi_fail_msg("gemv_splitk_ln: the fused LayerNorm needs N = 2048, ln_b, xn (ldxn % 8) and ldo % 8");
   if (epi != ZMI_EPI_RESIDUAL && epi != ZMI_EPI_STORE) return zmi_fail_msg("gemv_splitk: EPI_RESIDUAL or EPI_STORE only");
@@ -242,6 +270,16 @@ extern "C" int zmi_gemv_splitk_ln(const ZmiGemvArgs* args, int epi, float* part,
   if (a.M < 1 || a.ldx % 8 || a.ldo < a.N) return zmi_fail_msg("gemv_splitk: rows / strides");
   const int nseg = a.K == 8192 ? Shape<8192>::NSEG : (a.K == 4096 ? Shape<4096>::NSEG : Shape<2048>::NSEG);
   if (!part || part_floats < (int64_t)nseg * a.M * a.N) return zmi_fail_msg("gemv_splitk: partial buffer too small");
+  return 0;
+}
+
+extern "C" int zmi_gemv_splitk_ln(const ZmiGemvArgs* args, int epi, float* part, int64_t part_floats, const void* ln_w,
+                                  const void* ln_b, float eps, void* xn, int ldxn, void* stream) {
+  const ZmiGemvArgs& a = *args;
+  // before any launch: the kernel would read E4M3 bytes as bf16
+  if (a.w_fmt != ZMI_WFMT_BF16)
+    return zmi_fail_msg("gemv_splitk: bf16 weights only (fp8 weights run zmi_gemv_launch; fc2: zmi_gemv_splitk_f8)");
+  if (const int rc = check_splitk(a, epi, part, part_floats, ln_w, ln_b, xn, ldxn)) return rc;
   hipStream_t s = (hipStream_t)stream;
   if (a.K == 8192) return launch_splitk<8192>(a, epi, part, ln_w, ln_b, eps, xn, ldxn, s);
   if (a.K == 4096) return launch_splitk<4096>(a, epi, part, ln_w, ln_b, eps, xn, ldxn, s);
@@ -250,4 +288,22 @@ extern "C" int zmi_gemv_splitk_ln(const ZmiGemvArgs* args, int epi, float* part,
 
 extern "C" int zmi_gemv_splitk(const ZmiGemvArgs* args, int epi, float* part, int64_t part_floats, void* stream) {
   return zmi_gemv_splitk_ln(args, epi, part, part_floats, nullptr, nullptr, 0.f, nullptr, 0, stream);
+}
+
+// fc2 over fp8 weights (layout M8F8): the same split, the bytes expanded to bf16 registers once per workgroup, the
+// column's 2^e applied to the finished sum by the reduce
+extern "C" int zmi_gemv_splitk_f8_ln(const ZmiGemvArgs* args, int epi, float* part, int64_t part_floats,
+                                     const void* ln_w, const void* ln_b, float eps, void* xn, int ldxn, void* stream) {
+  const ZmiGemvArgs& a = *args;
+  // before any launch: the kernel would read bf16 weights as E4M3 bytes, or exponents through a NULL pointer
+  if (a.w_fmt != ZMI_WFMT_FP8 || !a.w_exp || ((size_t)a.w_exp & 7))
+    return zmi_fail_msg("gemv_splitk_f8: fp8 weights with w_exp (8-byte aligned) only (bf16 weights: zmi_gemv_splitk)");
+  if (a.K != 8192 || epi != ZMI_EPI_RESIDUAL)
+    return zmi_fail_msg("gemv_splitk_f8: K = 8192 with EPI_RESIDUAL (fc2) only");
+  if (const int rc = check_splitk(a, epi, part, part_floats, ln_w, ln_b, xn, ldxn)) return rc;
+  return launch_splitk<8192, ZMI_WFMT_FP8>(a, epi, part, ln_w, ln_b, eps, xn, ldxn, (hipStream_t)stream);
+}
+
+extern "C" int zmi_gemv_splitk_f8(const ZmiGemvArgs* args, int epi, float* part, int64_t part_floats, void* stream) {
+  return zmi_gemv_splitk_f8_ln(args, epi, part, part_floats, nullptr, nullptr, 0.f, nullptr, 0, stream);
 }

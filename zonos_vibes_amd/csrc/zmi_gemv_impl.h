@@ -721,10 +721,17 @@ __device__ __forceinline__ void dma_dword(const void* gsrc, void* ldp) {
 }
 
 //  * DN (dense pairs, zmi_gemv_row.h): each wave owns one PAIR of groups; half the MFMAs of the M8 form, same bits.
-template <int EPI, int GPW, bool DN = false>
-__global__ __launch_bounds__(GR_G * 4 / GPW * 64 / (DN ? 2 : 1)) void gemm_rows_kernel(const ZmiGemvArgs a, int n_cb,
-                                                                                       int n_rt, int rpw) {
+//  * FMT fp8 (layout M8F8): half the weight loads (512-byte chunks, two per 16-byte load); once they have landed the
+//    bytes are expanded into the bf16 registers of the bf16 form (expand_fp8: once per workgroup, not per tile as
+//    gemv_body's chain does), the tile loop is the bf16 one, and the epilogue wave scales its group's finished sums by
+//    the columns' 2^e (ColSum), as gemv_body does. No wait is added: the exponents land under the ZMI_WAIT_VM(0) below.
+template <int EPI, int GPW, bool DN, int FMT>
+__device__ __forceinline__ void gemm_rows_body(const ZmiGemvArgs& a, int n_cb, int n_rt, int rpw, char* smem) {
   constexpr int W = 4, NL = 8, RT = GR_RT, K = 2048, KC = K / 64, XROW = GR_XROW, NE = 2;
+  constexpr bool F8 = FMT == ZMI_WFMT_FP8;
+  static_assert(FMT == ZMI_WFMT_BF16 || F8, "weight format");
+  static_assert(!F8 || EPI == ZMI_EPI_SWIGLU || EPI == ZMI_EPI_RESIDUAL || EPI == ZMI_EPI_F32,
+                "fp8 weights: the MLP epilogues (pro_built)");
   // group sets (DN: pair sets, GPW pairs per wave), waves
   constexpr int NGS = DN ? GR_G / 2 / GPW : GR_G / GPW, NWV = NGS * W;
   static_assert(!DN || GPW == 1, "dense pairs: one pair per wave");
@@ -735,7 +742,6 @@ __global__ __launch_bounds__(GR_G * 4 / GPW * 64 / (DN ? 2 : 1)) void gemm_rows_
   // operand pieces per tile, issued by the last wave: residual inputs (16 rows x 8 groups x 16 B), or the rows'
   // positions and cache rows (dwords)
   constexpr int EP = EPI == ZMI_EPI_RESIDUAL ? 2 : (EPI == ZMI_EPI_QKV ? 1 : 0);
-  extern __shared__ __attribute__((aligned(16))) char smem[];
   bf16_t* xs = reinterpret_cast<bf16_t*>(smem);                 // [2][RT][XROW] activation tiles
   float* red = reinterpret_cast<float*>(smem + GR_RED);          // [group][segment][8][RT] segment sums
   char* ops = smem + GR_OPS;                                     // [2][2 KiB]
@@ -795,7 +801,22 @@ __global__ __launch_bounds__(GR_G * 4 / GPW * 64 / (DN ? 2 : 1)) void gemm_rows_
   // the weight slices of the wave's groups (GPW NL x 16 B per lane), in flight at once (all waited for below, before
   // the first chain). Re-read by the other row groups of this column block from L2 (temporal).
   u32x4_t wf[DN ? 2 : GPW][NL];  // DN: wf[h][j] = k-half h of chunk j for the wave's pair
-  if constexpr (DN) {
+  u32x4_t raw[F8 ? (DN ? 2 : GPW) : 1][NL / 2];  // fp8: the landed pieces, dead once expanded into wf
+  uint2 wexp = {0u, 0u};                         // fp8: the 8 column exponents of this wave's epilogue group
+  if constexpr (F8) {
+    // (every wave loads: the address is wave-uniform and clamped like gg[]; only the epilogue waves use it)
+    wexp = *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(a.w_exp) + 8 * min(eg, ngroups - 1));
+    if constexpr (DN) {
+      const int grp = min(cb * GR_G + 2 * gs + dn_member(lane), ngroups - 1) - cb * GR_G;
+      load_weights_dn_f8<NL, 0>(reinterpret_cast<const char*>(a.W) + (size_t)cb * GR_G * KC * 512, GR_G * KC * 512,
+                                (grp * KC + wk * NL) * 512, lane, raw);
+    } else {
+#pragma unroll
+      for (int h = 0; h < GPW; ++h)
+        load_weights_m8<NL / 2, 0>(reinterpret_cast<const char*>(a.W) + ((size_t)gg[h] * KC + wk * NL) * 512, NL * 512,
+                                   lane, raw[h]);
+    }
+  } else if constexpr (DN) {
     // lane l: column l & 15 of pair gs (group cb * 8 + 2 gs + dn_member(l), clamped: discarded); the descriptor
     // spans the column block's 8 groups
     const int grp = min(cb * GR_G + 2 * gs + dn_member(lane), ngroups - 1) - cb * GR_G;
@@ -812,6 +833,12 @@ __global__ __launch_bounds__(GR_G * 4 / GPW * 64 / (DN ? 2 : 1)) void gemm_rows_
   // waits for the weights out of the tile loop (a vmcnt(0) there would also wait for the DMA of later tiles
   // and for the epilogue stores)
   ZMI_WAIT_VM(0);
+  if constexpr (F8) {  // the landed bytes become the bf16 form's registers, once for all of the workgroup's tiles
+#pragma unroll
+    for (int h = 0; h < (DN ? 2 : GPW); ++h) expand_fp8<NL>(raw[h], wf[h]);
+    wexp.x = __builtin_amdgcn_readfirstlane(wexp.x);
+    wexp.y = __builtin_amdgcn_readfirstlane(wexp.y);
+  }
   __syncthreads();
 
   for (int t = t0;; ++t) {  // invariant: tile t's rows and operands are in LDS, visible to every wave
@@ -876,8 +903,8 @@ __global__ __launch_bounds__(GR_G * 4 / GPW * 64 / (DN ? 2 : 1)) void gemm_rows_
     if (ti == 1) ZMI_GSTAMP(4);
     if (t + 2 < rt_end) dma_tile(t + 2);
     if (ew) {  // group cb * 8 + wave: its segment sums in segment order (gemv_body's wave order)
-      epilogue<EPI, RT, 0>(a, ColSum<W, RT>{red + wave * W * 8 * RT}, lane, rows, row0, eg, res_pre, q_pos, q_kvr,
-                           QkvFuse{nullptr, 0});
+      epilogue<EPI, RT, 0>(a, ColSum<W, RT, F8>{red + wave * W * 8 * RT, wexp}, lane, rows, row0, eg, res_pre, q_pos,
+                           q_kvr, QkvFuse{nullptr, 0});
       if (more && lane == 0) __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
     if (ti == 1) ZMI_GSTAMP(5);
@@ -886,6 +913,19 @@ __global__ __launch_bounds__(GR_G * 4 / GPW * 64 / (DN ? 2 : 1)) void gemm_rows_
   ZMI_GSTAMP(7);
 }
 
+template <int EPI, int GPW, bool DN = false>
+__global__ __launch_bounds__(GR_G * 4 / GPW * 64 / (DN ? 2 : 1)) void gemm_rows_kernel(const ZmiGemvArgs a, int n_cb,
+                                                                                       int n_rt, int rpw) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  gemm_rows_body<EPI, GPW, DN, ZMI_WFMT_BF16>(a, n_cb, n_rt, rpw, smem);
+}
+// the same launch over fp8 weights (a kernel of its own name, as gemv_kernel_f8)
+template <int EPI, int GPW, bool DN = false>
+__global__ __launch_bounds__(GR_G * 4 / GPW * 64 / (DN ? 2 : 1)) void gemm_rows_kernel_f8(const ZmiGemvArgs a, int n_cb,
+                                                                                          int n_rt, int rpw) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  gemm_rows_body<EPI, GPW, DN, ZMI_WFMT_FP8>(a, n_cb, n_rt, rpw, smem);
+}
 
 // row tiles per workgroup: enough workgroups to fill the chip (~4 per CU), each re-reading its weight
 // slice as few times as that allows (speed only: a row's arithmetic does not depend on it)
@@ -938,10 +978,22 @@ inline int groups_for(const ZmiGemvArgs& a, const Shape& s) {
 // 64 rows qkv 12.1 -> 9.6, fc1 26.2 -> 22.8, heads 21.3 -> 15.3 but out_proj 5.8 -> 6.8; 32 rows only the
 // wide ones (heads 13.3 -> 11.6; qkv 7.6 -> 9.7, out_proj 5.8 -> 8.3)
 inline bool rows_form(int M, int N) { return M > 64 || (M > 32 && N >= 3072) || N >= 8192; }
-// the launches that take the many-row form: plain bf16 K = 2048 rows past one tile, no forced group count
-inline bool rows_launch(const ZmiGemvArgs& a) {
-  return a.w_fmt == ZMI_WFMT_BF16 && a.K == 2048 && a.M > GR_RT && a.ln_w == nullptr && a.pro == ZMI_PRO_AUTO &&
-         a.groups == 0 && zmi_option(ZMI_OPT_GEMM_ROWS) && rows_form(a.M, a.N);
+// the launches that take the many-row form: plain K = 2048 rows past one tile, no forced group count; over fp8 weights
+// the MLP epilogues pro_built(2048, epi, PRO_PLAIN, true) names other than STORE (the plain fp8 STORE at K = 2048 is
+// not built in any form), while ZMI_OPT_FP8_ROWS is set (0: gemv_body's tile loop, the same bits). rows_form's
+// thresholds hold for fp8 as they are: fc1 (N 16384, SWIGLU, weights streamed from HBM) per launch, fp8 tile loop ->
+// fp8 many-row form, median of 5 (max - min of both arms): 24 rows 13.4 -> 11.5 us (0.3), 32 14.2 -> 11.7 (0.2), 48
+// 17.5 -> 13.2 (0.6), 64 21.8 -> 14.9 (0.8), 128 36.7 -> 21.2 (1.1), 322 84.4 -> 41.8 (1.4); the bf16 many-row form
+// 18.6 / 18.8 / 20.4 / 21.9 / 28.1 / 48.3 (tools/bench_fp8_rows.py, profiles/fp8_rows_bench.json)
+inline bool rows_launch(const ZmiGemvArgs& a, int epi) {
+  if (a.w_fmt == ZMI_WFMT_FP8) {
+    if (!zmi_option(ZMI_OPT_FP8_ROWS) || (epi != ZMI_EPI_SWIGLU && epi != ZMI_EPI_RESIDUAL && epi != ZMI_EPI_F32))
+      return false;
+  } else if (a.w_fmt != ZMI_WFMT_BF16) {
+    return false;
+  }
+  return a.K == 2048 && a.M > GR_RT && a.ln_w == nullptr && a.pro == ZMI_PRO_AUTO && a.groups == 0 &&
+         zmi_option(ZMI_OPT_GEMM_ROWS) && rows_form(a.M, a.N);
 }
 
 // gemv_body's (G, W, NL, RT) instantiations that are built with every prologue / tile form of launch_g; the 4-group
@@ -979,9 +1031,10 @@ inline bool form_for(const ZmiGemvArgs& a, int epi, ZmiGemvForm* f) {
   Shape sh;
   if (!shape_for(a.K, &sh)) return false;
   const bool f8 = a.w_fmt == ZMI_WFMT_FP8;
-  // fp8 weights run gemv_body's tile loop for every M: the many-row form (and the split-K GEMM) read bf16 weights
-  // only. All forms agree bit for bit, so this costs many-row speed, never bits. (Which fp8 launches exist: pro_built.)
-  if (rows_launch(a)) {
+  // fp8 weights take the many-row form where bf16 ones do (the MLP epilogues; ZMI_OPT_FP8_ROWS 0: gemv_body's tile
+  // loop for every M). All forms agree bit for bit, so the choice is speed, never bits. (Which fp8 launches exist:
+  // pro_built; fc2's split-K over fp8 bytes is zmi_gemv_splitk_f8.)
+  if (rows_launch(a, epi)) {
     const int n_cb = (a.N / 8 + GR_G - 1) / GR_G, n_rt = (a.M + GR_RT - 1) / GR_RT;
     *f = {(zmi_option(ZMI_OPT_GEMM_ROWS) & 2) ? ZMI_FORM_ROWS_DENSE : ZMI_FORM_ROWS, GR_G, 4, 8, GR_RT, 0, PRO_PLAIN,
           n_cb, n_rt, rows_per_wg(n_cb, n_rt, zmi_cu_count())};  // one workgroup per CU
@@ -1052,9 +1105,17 @@ hipError_t launch_g(const ZmiGemvArgs& a, hipStream_t s, const ZmiGemvForm& f) {
   return hipErrorInvalidValue;
 }
 
-template <int EPI, int GPW, bool DN>
+template <int FMT, int EPI, int GPW, bool DN>
+constexpr auto gemm_rows_fn() {  // the many-row kernel of a weight format (only the one asked for is instantiated)
+  if constexpr (FMT == ZMI_WFMT_FP8)
+    return &gemm_rows_kernel_f8<EPI, GPW, DN>;
+  else
+    return &gemm_rows_kernel<EPI, GPW, DN>;
+}
+
+template <int EPI, int GPW, bool DN, int FMT = ZMI_WFMT_BF16>
 hipError_t launch_rows(const ZmiGemvArgs& a, hipStream_t s, const ZmiGemvForm& f) {
-  auto fn = gemm_rows_kernel<EPI, GPW, DN>;
+  auto fn = gemm_rows_fn<FMT, EPI, GPW, DN>();
   const int64_t blocks = block_count(f.n_cb, f.n_rt, f.rpw);
   static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(fn),
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX);
@@ -1084,6 +1145,12 @@ template <int EPI>
 hipError_t launch(const ZmiGemvArgs& a, hipStream_t s) {
   ZmiGemvForm f;
   if (!form_for(a, EPI, &f)) return hipErrorInvalidValue;
+  if (a.w_fmt == ZMI_WFMT_FP8 && (f.kind == ZMI_FORM_ROWS_DENSE || f.kind == ZMI_FORM_ROWS)) {
+    if constexpr (EPI == ZMI_EPI_SWIGLU || EPI == ZMI_EPI_RESIDUAL || EPI == ZMI_EPI_F32)  // rows_launch's fp8 epilogues
+      return f.kind == ZMI_FORM_ROWS_DENSE ? launch_rows<EPI, 1, true, ZMI_WFMT_FP8>(a, s, f)
+                                           : launch_rows<EPI, 2, false, ZMI_WFMT_FP8>(a, s, f);
+    return hipErrorInvalidValue;
+  }
   if (f.kind == ZMI_FORM_ROWS_DENSE) return launch_rows<EPI, 1, true>(a, s, f);
   if (f.kind == ZMI_FORM_ROWS) return launch_rows<EPI, 2, false>(a, s, f);
   if (a.w_fmt == ZMI_WFMT_FP8) {

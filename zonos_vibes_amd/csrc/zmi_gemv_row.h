@@ -65,6 +65,34 @@ __device__ __forceinline__ void load_weights_dn(const char* base, int span, int 
     for (int h = 0; h < 2; ++h) wh[h][j] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, vo + 128 * h, j * 1024, POLICY);
 }
 
+// DN over M8F8 bytes: the same M8 lane of the pair's group, in the 1 KiB fp8 pieces (group_off in fp8 bytes, 512 per
+// chunk). The 16 bytes at that lane of piece p are k-half h of chunk 2p (bytes 0..7) and of chunk 2p + 1 (bytes 8..15):
+// NL / 2 loads per k-half. raw[h][p] expands to wh[h][2p], wh[h][2p + 1] (expand_fp8).
+template <int NL, int POLICY>
+__device__ __forceinline__ void load_weights_dn_f8(const char* base, int span, int group_off, int lane,
+                                                   u32x4_t (&raw)[2][NL / 2]) {
+  const __amdgpu_buffer_rsrc_t rsrc =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(base), (short)0, span, 0x00020000);
+  const int vo = group_off + ((lane & 7) + 16 * (lane >> 4)) * 16;
+#pragma unroll
+  for (int p = 0; p < NL / 2; ++p)
+#pragma unroll
+    for (int h = 0; h < 2; ++h) raw[h][p] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, vo + 128 * h, p * 1024, POLICY);
+}
+// The many-row forms (gemm_rows_kernel, the split-K GEMM) run many row tiles over one weight slice, so they expand
+// the landed fp8 pieces ONCE into the bf16 registers the bf16 form holds and run its tile loop unchanged: raw[p] ->
+// wf[2p] (dwords 0, 1), wf[2p + 1] (dwords 2, 3), the operands chain_m8<NL, true> builds per tile. Through
+// fp8x8_to_bf16x8 (v_cvt_pk_f32_fp8 + v_perm_b32, exact) rather than gfx950's scaled packed fp8 -> bf16 converts: this
+// runs once per workgroup, off the tile loop, and stays the conversion every other fp8 form is tested with.
+template <int NL>
+__device__ __forceinline__ void expand_fp8(const u32x4_t (&raw)[NL / 2], u32x4_t (&wf)[NL]) {
+#pragma unroll
+  for (int p = 0; p < NL / 2; ++p) {
+    wf[2 * p] = __builtin_bit_cast(u32x4_t, fp8x8_to_bf16x8(raw[p][0], raw[p][1]));
+    wf[2 * p + 1] = __builtin_bit_cast(u32x4_t, fp8x8_to_bf16x8(raw[p][2], raw[p][3]));
+  }
+}
+
 // ---- MFMA chain over a wave's k-segment of NL 64-k chunks. `xa`: the lane's A fragment in the LDS rows, row l & 15 of
 // the tile (the caller clamps rows past it), k = 8 (l >> 4) .. + 7; chunk j's k-half 0 at xa + 64 j, k-half 1 at + 32.
 // Against k-half 0 the tile's columns 0..7 are exact partial sums (acc0), against k-half 1 its columns 8..15 (acc1).

@@ -21,10 +21,11 @@ extern "C" const char* zmi_last_error(void) { return g_err; }
 // 4: zmi_dac_conv / conv_t / conv_out take channel-blocked multi-tap weights [tap][ci / 32][co][32] (round 5), the
 //    ZMI_OPT_GEMM_ROWS bit meanings of round 5; 5: ZMI_OPT_XC_HANDOFF (option 2) and zmi_xcd_dealing (round 6);
 //    6: ZMI_PRO_GRMS_G and ZmiMamba2Args.gz_g (round 6)
+//    (10 still with zmi_gemv_splitk_f8 / _f8_ln and ZMI_OPT_FP8_ROWS: no layout, struct or option changed meaning)
 extern "C" int zmi_version(void) { return 10; }
 
 // launch-geometry knobs (speed only: no option changes a result bit); defaults in the table
-static int g_opts[ZMI_OPT_COUNT] = {1, 3, 0, 0, 1, 8, 2, 1, 1, 0, 1, 256, 5, 29, 128, 0, 256, 1};
+static int g_opts[ZMI_OPT_COUNT] = {1, 3, 0, 0, 1, 8, 2, 1, 1, 0, 1, 256, 5, 29, 128, 0, 256, 1, 1};
 int zmi_option(int which) { return (which >= 0 && which < ZMI_OPT_COUNT) ? g_opts[which] : 0; }
 extern "C" int zmi_set_option(int which, int value) {
   if (which < 0 || which >= ZMI_OPT_COUNT) return zmi_fail_msg("zmi_set_option: unknown option");

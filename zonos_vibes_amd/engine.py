@@ -209,6 +209,15 @@ class HipEngine:
         # the hybrid's Mamba2 out_proj (K = d_ssm = 4096, EPI_STORE) over >= `splitk_m_rows` rows (its prefill: the
         # GEMV form re-read every row's 8 KB activation row per 8-column group, 67 us at 322 rows)
         self.splitk_m_rows = 16
+        # weights="fp8": the MLP projections over many rows take the launch forms the bf16 ones take: fc1 the many-row
+        # form (ZMI_OPT_FP8_ROWS), fc2 over >= `splitk_rows` rows the split-K GEMM on fp8 bytes (zmi_gemv_splitk_f8,
+        # with the next LayerNorm in its reduce). False: gemv_body's tile loop for every row count. Identical bits
+        # either way; call _build_plan() after changing it (plans and captured graphs hold the choice). fc2 + the
+        # next LayerNorm per launch, tile loop + zmi_layernorm_rows -> zmi_gemv_splitk_f8_ln: 24 rows 14.8 -> 10.9 us,
+        # 64 22.5 -> 15.2, 128 37.5 -> 22.2, 322 87.0 -> 38.8 (spreads under 0.6), so `splitk_rows` serves both
+        # formats; C3 share 8.90 -> 7.33 s (bf16 7.78), an admission of 64 requests 508 -> 260 ms (bf16 262)
+        # (profiles/fp8_rows_bench.json)
+        self.fp8_rows = True
         # decode steps whose slots all sample greedily use the one-workgroup-per-slot sampler
         # (zmi_sample_step_greedy: identical results, no in-launch hand-off between codebooks)
         self.greedy_sampler = True
@@ -406,16 +415,38 @@ class HipEngine:
             _lib.check(self.lib.zmi_gemv_splitk(ctypes.byref(a), epi, self.splitk_part.data_ptr(),
                                                 self.splitk_part.numel(), self.sptr), "gemv_splitk")
             return
+        if self._use_splitk8(a, epi):
+            _lib.check(self.lib.zmi_gemv_splitk_f8(ctypes.byref(a), epi, self.splitk_part.data_ptr(),
+                                                   self.splitk_part.numel(), self.sptr), "gemv_splitk_f8")
+            return
+        if a.w_fmt == _lib.WFMT_FP8 and not self.fp8_rows:
+            # the library's many-row form is a process-wide option: off around this engine's fp8 launches only
+            # (the form is chosen on the host at launch, so a captured graph keeps it)
+            was = self.lib.zmi_get_option(_lib.OPT_FP8_ROWS)
+            _lib.check(self.lib.zmi_set_option(_lib.OPT_FP8_ROWS, 0), "set_option")
+            try:
+                _lib.check(self.lib.zmi_gemv_launch(ctypes.byref(a), epi, self.sptr), "gemv")
+            finally:
+                _lib.check(self.lib.zmi_set_option(_lib.OPT_FP8_ROWS, was), "set_option")
+            return
         _lib.check(self.lib.zmi_gemv_launch(ctypes.byref(a), epi, self.sptr), "gemv")
 
     def _use_splitk(self, a, epi) -> bool:
         lo = {8192: self.splitk_rows, 2048: self.splitk_o_rows, 4096: self.splitk_m_rows}.get(a.K, 0)
         want = _lib.EPI_STORE if a.K == 4096 else _lib.EPI_RESIDUAL  # 4096: the hybrid's Mamba2 out_proj (d_ssm)
-        # (fp8 weights: the split-K GEMM reads bf16 only; gemv_body's tile loop gives the same bits)
+        # (fp8 weights: zmi_gemv_splitk reads bf16 only; fc2 over fp8 bytes is _use_splitk8's entry point)
         return (lo > 0 and a.M >= lo and epi == want and not a.ln_w and a.pro == _lib.PRO_AUTO
                 and a.w_fmt == _lib.WFMT_BF16
                 and a.N % 64 == 0 and a.n_valid == a.N
                 and a.M * a.N * (8 if a.K == 8192 else 4) <= self.splitk_part.numel())
+
+    def _use_splitk8(self, a, epi) -> bool:
+        """fc2 over fp8 weights as the split-K GEMM on fp8 bytes (zmi_gemv_splitk_f8): _use_splitk's conditions for
+        K = 8192, while fp8_rows is set."""
+        return (self.fp8_rows and a.w_fmt == _lib.WFMT_FP8 and a.K == 8192 and epi == _lib.EPI_RESIDUAL
+                and self.splitk_rows > 0 and a.M >= self.splitk_rows and not a.ln_w and a.pro == _lib.PRO_AUTO
+                and a.N % 64 == 0 and a.n_valid == a.N
+                and a.M * a.N * 8 <= self.splitk_part.numel())
 
     def _build_plan(self):
         """Invalidate the per-row-count decode plans and graphs (new weights or buffers)."""
@@ -547,6 +578,9 @@ class HipEngine:
                     # the split-K reduce also writes LayerNorm(new x) for the next op (no pre-pass launch)
                     plan.append(("splitkln", (fc2, nxt)))
                     ln_ready[0] = True
+                elif pre and (last or not fused) and self._use_splitk8(*fc2) and d == 2048:
+                    plan.append(("splitk8ln", (fc2, nxt)))  # the same over fp8 weights
+                    ln_ready[0] = True
                 else:
                     plan.append(("gemv", fc2))
             xin, ln = normed((w["nf_w"], w["nf_b"]))
@@ -674,6 +708,12 @@ class HipEngine:
                 _lib.check(self.lib.zmi_gemv_splitk_ln(ctypes.byref(a), epi, self.splitk_part.data_ptr(),
                                                        self.splitk_part.numel(), ln[0].data_ptr(), ln[1].data_ptr(),
                                                        self.eps, self.xn.data_ptr(), self.d, self.sptr), "gemv_splitk_ln")
+            elif kind == "splitk8ln":
+                (a, epi), ln = item
+                _lib.check(self.lib.zmi_gemv_splitk_f8_ln(ctypes.byref(a), epi, self.splitk_part.data_ptr(),
+                                                          self.splitk_part.numel(), ln[0].data_ptr(), ln[1].data_ptr(),
+                                                          self.eps, self.xn.data_ptr(), self.d, self.sptr),
+                           "gemv_splitk_f8_ln")
             elif kind == "attn":
                 # decode: query row r caches into KV row r, so no row table (kv_row = NULL)
                 i, pf = item if isinstance(item, tuple) else (item, None)  # (layer, prefetch) or a KV layer index
