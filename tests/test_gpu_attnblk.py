@@ -16,13 +16,15 @@ D, H, HKV, HD = 2048, 16, 4, 128
 QKV_N = (H + 2 * HKV) * HD
 
 
-def _setup(positions, smax, seed):
+def _setup(positions, smax, seed, kscale=1.0):
+    """kscale multiplies the K cache: at 1.0 the scores are nearly flat (every block maximum about equal, so the
+    block recursion's exp(M_{j-1} - M_j) is about 1); at 8.0 they spread over several units and every fold rescales."""
     from zonos_vibes_amd.engine import rope_table
     R = len(positions)
     W = rnd(QKV_N, D, scale=0.03, seed=seed)
     X = rnd(R, D, scale=2.0, seed=seed + 1)
     lw, lb = rnd(D, scale=0.1, seed=seed + 2) + 1, rnd(D, scale=0.02, seed=seed + 3)
-    kc = rnd(R, HKV, smax, HD, seed=seed + 4)
+    kc = rnd(R, HKV, smax, HD, seed=seed + 4) * kscale
     vt = rnd(R, HKV, HD, smax, seed=seed + 5)
     return dict(W=pack(W), X=X, ln=(lw.contiguous(), lb.contiguous()), kc=kc, vt=vt, rope=rope_table(HD).to(DEV),
                 row_kv=torch.arange(R, dtype=torch.int32, device=DEV),
@@ -94,20 +96,35 @@ SELF, SPLIT = 256, 512  # zmi_attn_block slices flags: self-scoring / chunk-spli
 @pytest.mark.parametrize("slices", [4, 8, 4 | SELF, 8 | SELF, 8 | SPLIT])
 @pytest.mark.parametrize("smax", [1280, 2056])
 def test_attn_block_bit_identical_to_separate_launches(positions, slices, smax):
+    positions, live, got = _bit_identical(positions, slices, smax)
+    # and the output is the reference attention of the projected q / K / V
+    pick = live[:3]
+    _check_attention(got[3][pick], got[0][pick], got[1][pick], got[2][pick].transpose(-1, -2).contiguous(),
+                     [positions[i] for i in pick])
+
+
+def _bit_identical(positions, slices, smax, kscale=1.0):
     if slices & (SELF | SPLIT):  # these forms reach position 1023: keep the edges inside it
         positions = tuple(p if p < 1024 else p - 256 for p in positions) + ((1023,) if len(positions) < 16 else ())
     assert max(positions) <= _lib().lib().zmi_attn_block_max_pos(slices)
-    st = _setup(positions, smax, seed=70)
+    st = _setup(positions, smax, seed=70, kscale=kscale)
     ref = _separate(st)
     got = _fused(st, slices, reps=3)
     live = [i for i, p in enumerate(positions) if p >= 0]
     for name, r, g in zip(("q", "k_cache", "v_cache"), ref[:3], got[:3]):
         assert torch.equal(r, g), name
     assert torch.equal(ref[3][live], got[3][live]), "attention output"
-    # and the output is the reference attention of the projected q / K / V
-    pick = live[:3]
-    _check_attention(got[3][pick], got[0][pick], got[1][pick], got[2][pick].transpose(-1, -2).contiguous(),
-                     [positions[i] for i in pick])
+    return positions, live, got
+
+
+@pytest.mark.parametrize("slices", [4, 8, 4 | SELF, 8 | SELF, 8 | SPLIT])
+@pytest.mark.parametrize("smax", [1280, 2056])
+def test_attn_block_bit_identical_on_spread_scores(slices, smax):
+    """The bit-identity above with the K cache scaled by 8: block maxima differ by several units, so every step of
+    the block recursion rescales acc and l (a fold that dropped a rescale would change almost no bit of the flat
+    cases). Only the equalities: _check_attention's tolerance was set for flat scores, and
+    test_gpu_attn_probe.py holds the chunked kernel itself to fp64 on spread scores."""
+    _bit_identical((127, 128, 511, 512, 1030, 1279), slices, smax, kscale=8.0)
 
 
 @pytest.mark.parametrize("positions", [
@@ -120,15 +137,26 @@ def test_attn_block_bit_identical_to_separate_launches(positions, slices, smax):
 def test_attn_block_wide_split_bit_identical_to_separate_launches(positions, smax):
     """The 24-chunk split form (batch-1 decode steps past the 8-chunk reach, up to position 3071): q, the KV
     cache writes and the attention output bit-identical to the QKV GEMV + chunked attention launches."""
+    got = _wide_bit_identical(positions, smax)
+    _check_attention(got[3][:2], got[0][:2], got[1][:2], got[2][:2].transpose(-1, -2).contiguous(), list(positions[:2]))
+
+
+def _wide_bit_identical(positions, smax, kscale=1.0):
     slices = 24 | SPLIT
     assert max(positions) <= _lib().lib().zmi_attn_block_max_pos(slices) == 3071
-    st = _setup(positions, smax, seed=72)
+    st = _setup(positions, smax, seed=72, kscale=kscale)
     ref = _separate(st)
     got = _fused(st, slices, reps=3)
     for name, r, g in zip(("q", "k_cache", "v_cache"), ref[:3], got[:3]):
         assert torch.equal(r, g), name
     assert torch.equal(ref[3], got[3]), "attention output"
-    _check_attention(got[3][:2], got[0][:2], got[1][:2], got[2][:2].transpose(-1, -2).contiguous(), list(positions[:2]))
+    return got
+
+
+@pytest.mark.parametrize("smax", [3072, 3200])
+def test_attn_block_wide_split_bit_identical_on_spread_scores(smax):
+    """The 24-chunk form on the K cache scaled by 8 (six 512-key blocks, every fold rescales): equalities only."""
+    _wide_bit_identical((0, 1, 1535, 1536, 2047, 2048, 2559, 3071), smax, kscale=8.0)
 
 
 @pytest.mark.parametrize("slices", [8, 8 | SELF, 8 | SPLIT, 24 | SPLIT])
@@ -161,13 +189,26 @@ def test_attn_block_refuses_positions_past_its_reach(slices):
     ((3071, 2047, 1535, 1536), 24),                  # the form's last position, block edges
 ])
 def test_attn_block_oproj_bit_identical_to_separate_launches(positions, chunks):
+    _oproj_bit_identical(positions, chunks)
+
+
+@pytest.mark.parametrize("positions,chunks", [
+    ((127, 128, 511, 512, 900, 1023), 8),
+    ((3071, 2047, 1535, 1536), 24),
+])
+def test_attn_block_oproj_bit_identical_on_spread_scores(positions, chunks):
+    """The fused out_proj forms on the K cache scaled by 8 (every fold of the block recursion rescales)."""
+    _oproj_bit_identical(positions, chunks, kscale=8.0)
+
+
+def _oproj_bit_identical(positions, chunks, kscale=1.0):
     """zmi_attn_block_oproj (a chunk-split form, 8 or 24 chunk workgroups, with the layer's out_proj GEMV in the same
     launch, its input gathered from the merging workgroups' granules): q, K / V, the attention output and the new
     residual rows bit-identical to the QKV GEMV + attention + out_proj GEMV (EPI_RESIDUAL) launches; run twice (the
     second launch finds its own granules from the first: equal values, equal tags)."""
     L = _lib()
     slices = chunks | SPLIT
-    st = _setup(positions, 2056 if chunks == 8 else 3080, seed=80)
+    st = _setup(positions, 2056 if chunks == 8 else 3080, seed=80, kscale=kscale)
     R = st["R"]
     ref_q, ref_k, ref_v, ref_out = _separate(st)
     Wo = pack(rnd(D, H * HD, scale=0.03, seed=81))[0]

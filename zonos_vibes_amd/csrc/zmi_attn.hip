@@ -41,15 +41,12 @@ using namespace zmi_attn;
 constexpr int NT = NWC * 64;
 constexpr unsigned SPIN_LIMIT = 1u << 20;
 
-
-
-
 // MODE 0: one launch, the cross-chunk maxima exchanged by granules while the chunks wait. MODE 1 + MODE 2: two
 // launches with no waiting: 1 computes the chunk's scores and maxima and leaves them in its own partial slots
 // (scores in part_o, maxima in part_lm's M word); 2 forms M_j from those maxima, reads its scores back and
 // finishes as MODE 0 does. MODE 3 is MODE 2 without the ticket: it leaves its chunk partial (plain stores) for
 // attn_merge_kernel, a third launch. All give the same bits: max is exact in any order, every other step is shared
-// code (merge2 performs merge4's operations per element).
+// code (zmi_attn_merge.h; mergeN runs the same ChunkFold per element for 2 or 4 dims).
 template <int G, int MODE>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(G == 4 ? 6 : 1, 8))) void attn_kernel(const AttnArgs a) {
   __shared__ float sc[G][CH];
@@ -150,6 +147,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(G == 4 ? 6 :
     __syncthreads();
   }
   // ---- scores s = fp32(q . k) * scale (dim blocks in order per key tile); keys past the position are -inf ----
+  // (mirrors score_tile / q_frag_lds, the two tiles' chains interleaved: fewer VGPRs under the loads)
   f32x4_t st[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
   for (int db = 0; db < 4; ++db) {
@@ -232,12 +230,13 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(G == 4 ? 6 :
   // ---- P.V: this wave's 32 keys x 128 dims (V of keys past the position is zeroed: never let
   // stale cache bytes into the sum) ----
   {
+    // (mirrors p_frag, the index computed inside the branch: an occupancy step for G = 1 / 2)
     uint4 pf = uint4{0u, 0u, 0u, 0u};
     if (c16 < G) pf = *reinterpret_cast<const uint4*>(&pb[c16][wave * 32 + 8 * h4]);
     const int kbase = wave * 32 + 8 * h4;  // first key of this lane's 8 positions
 #pragma unroll
     for (int dt = 0; dt < 8; ++dt) {
-      const f32x4_t o = mfma16(pf, v_keep(vf[dt], kbase, nkeys), f32x4_t{0.f, 0.f, 0.f, 0.f});
+      const f32x4_t o = pv_tile(pf, v_keep(vf[dt], kbase, nkeys));
       if (h4 == 0) {  // column = dim 16 dt + c16, row = head i
 #pragma unroll
         for (int i = 0; i < G; ++i) opart[wave][i][16 * dt + c16] = o[i];
@@ -304,14 +303,16 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(G == 4 ? 6 :
   if constexpr (MODE == 2) {  // 2 dims per thread, 16 chunks' loads in flight
     for (int e = t * 2; e < G * HD; e += NT * 2) {
       const int g = e / HD, d = e - g * HD;
-      const float2 r = merge2<16>(ou, lu, nc, g, d, G);
-      *reinterpret_cast<uint32_t*>(dst + e) = f2bf(r.x) | (f2bf(r.y) << 16);
+      float r[2];
+      mergeN<2, 16>(r, ou, lu, nc, g, d, G);
+      *reinterpret_cast<uint32_t*>(dst + e) = f2bf(r[0]) | (f2bf(r[1]) << 16);
     }
   } else {
     for (int e = t * 4; e < G * HD; e += NT * 4) {
       const int g = e / HD, d = e - g * HD;
-      const float4 r = merge4(ou, lu, nc, g, d, G);
-      *reinterpret_cast<uint2*>(dst + e) = uint2{f2bf(r.x) | (f2bf(r.y) << 16), f2bf(r.z) | (f2bf(r.w) << 16)};
+      float r[4];
+      mergeN<4, 8>(r, ou, lu, nc, g, d, G);
+      *reinterpret_cast<uint2*>(dst + e) = uint2{f2bf(r[0]) | (f2bf(r[1]) << 16), f2bf(r[2]) | (f2bf(r[3]) << 16)};
     }
   }
   ZMI_ASTAMP(7);
@@ -386,21 +387,17 @@ __global__ __launch_bounds__(BNT) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
   __syncthreads();  // q in LDS
   ZMI_ASTAMP(1);
   // ---- scores (the chunked kernel's chain per 16-key sub-tile); keys past the position are -inf ----
+  uint4 qf[4];
+  q_frag_lds<G>(qf, reinterpret_cast<const uint4*>(qs), c16, h4);
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
-    f32x4_t st[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-    for (int db = 0; db < 4; ++db) {
-      const uint4 qv = c16 < G ? *reinterpret_cast<const uint4*>(&qs[c16 * HD + 8 * h4 + 32 * db]) : uint4{0u, 0u, 0u, 0u};
-#pragma unroll
-      for (int tt = 0; tt < 2; ++tt) st[tt] = mfma16(qv, kf[k][tt][db], st[tt]);
-    }
 #pragma unroll
     for (int tt = 0; tt < 2; ++tt) {
+      const f32x4_t st = score_tile(qf, kf[k][tt]);
       const int key = 32 * (2 * wave + k) + 16 * tt + c16;  // block-local
       if (h4 == 0) {
 #pragma unroll
-        for (int i = 0; i < G; ++i) sc[i][key] = key < nkeys ? st[tt][i] * a.scale : -INFINITY;
+        for (int i = 0; i < G; ++i) sc[i][key] = key < nkeys ? st[i] * a.scale : -INFINITY;
       }
     }
   }
@@ -458,12 +455,11 @@ __global__ __launch_bounds__(BNT) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
     const int tl = 2 * wave + k;
-    uint4 pf = uint4{0u, 0u, 0u, 0u};
-    if (c16 < G) pf = *reinterpret_cast<const uint4*>(&pb[c16][32 * tl + 8 * h4]);
     const int kbase = 32 * tl + 8 * h4;
+    const uint4 pf = p_frag(pb, c16, kbase);
 #pragma unroll
     for (int dt = 0; dt < 8; ++dt) {
-      const f32x4_t o = mfma16(pf, v_keep(vf[k][dt], kbase, nkeys), f32x4_t{0.f, 0.f, 0.f, 0.f});
+      const f32x4_t o = pv_tile(pf, v_keep(vf[k][dt], kbase, nkeys));
       if (h4 == 0) {
 #pragma unroll
         for (int i = 0; i < G; ++i) opart[tl][i][16 * dt + c16] = o[i];
@@ -515,13 +511,12 @@ __global__ __launch_bounds__(BNT) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
   const float* lu = a.part_lm + (size_t)unit * a.nch * G * 2;
   for (int e = t; e < G * HD; e += BNT) {
     const int g = e / HD, d = e - g * HD;
-    float acc = 0.f, l = 0.f, mprev = 0.f;
+    ChunkFold<> f;
     for (int b = 0; b < nb; ++b) {
-      const float ob = ou[(size_t)b * G * HD + e];
       const float2 lm = ld2(lu + (size_t)b * G * 2 + 2 * g);
-      fold_block(acc, l, mprev, ob, lm.x, lm.y, b == 0);
+      f.block(ou[(size_t)b * G * HD + e], lm.x, lm.y, b == 0);
     }
-    dst[e] = (bf16_t)f2bf(acc * (1.0f / l));
+    dst[e] = (bf16_t)f2bf(f.out());
   }
   ZMI_ASTAMP(7);
 }
@@ -537,8 +532,9 @@ __global__ __launch_bounds__(64) void attn_merge_kernel(const AttnArgs a) {
   const float* ou = a.part_o + (size_t)unit * a.nch * G * HD;
   const float* lu = a.part_lm + (size_t)unit * a.nch * G * 2;
   const int d = threadIdx.x * 2;
-  const float2 r = merge2<16>(ou, lu, nc, g, d, G);
-  *reinterpret_cast<uint32_t*>(a.out + (size_t)qi * a.ldo + (kh * G + g) * HD + d) = f2bf(r.x) | (f2bf(r.y) << 16);
+  float r[2];
+  mergeN<2, 16>(r, ou, lu, nc, g, d, G);
+  *reinterpret_cast<uint32_t*>(a.out + (size_t)qi * a.ldo + (kh * G + g) * HD + d) = f2bf(r[0]) | (f2bf(r[1]) << 16);
 }
 
 template <int G, int DS>

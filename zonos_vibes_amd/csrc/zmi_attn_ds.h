@@ -5,14 +5,15 @@
 // its query: all scores and softmax statistics (K is read by each of the DS slices of a unit; they
 // share one XCD under round-robin placement, so most of them read it from L2), and P.V for its own
 // dims only. No workgroup waits on another. The arithmetic is zmi_attn.hip's chunked kernel's,
-// operation for operation, so every variant returns identical bits and the launcher may pick any:
-//   * scores per 32-key group: the same 4-MFMA chain over the same operand layout;
+// operation for operation, because both call zmi_attn_merge.h's statement of each step, so every
+// variant returns identical bits and the launcher may pick any:
+//   * scores per 16-key tile: score_tile over the same operand layout;
 //   * chunk maxima over CH keys; M_j over the chunks of blocks 0..j (max is exact);
-//   * per chunk and head: lane L takes keys L, L + 64 (e = 0 past the position), wave_sum -> l_c;
-//   * P.V per 32-key group from a zero accumulator, chunk o = group sums in group order (groups
+//   * per chunk and head: exp_lane (lane L takes keys L, L + 64; e = 0 past the position), wave_sum -> l_c;
+//   * P.V per 32-key group: p_frag, v_keep, pv_tile; chunk o = group sums in group order (groups
 //     wholly past the position contribute +0 there, which is the identity: an MFMA from a +0
 //     accumulator never returns -0, so they are skipped here);
-//   * zmi_attn_merge.h's block recursion per (head, dim).
+//   * ChunkFold per (head, dim).
 // Keys up to DS_KEYS: a wave holds the K and V^T fragments of all its groups (DKM per wave) in
 // registers, all issued before the first MFMA.
 
@@ -58,11 +59,6 @@ struct AttnArgs {
   int xc_l2;           // zmi_attn_block chunk-split form: hand-offs inside a unit through the XCD's L2 (ZMI_OPT_XC_HANDOFF)
 };
 
-__device__ __forceinline__ f32x4_t mfma16(const uint4& a, const uint4& b, f32x4_t c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c,
-                                                 0, 0, 0);
-}
-
 constexpr int DNW = 8;                    // waves per workgroup
 constexpr int DKM = 5;                    // 32-key groups per wave
 constexpr int DS_KEYS = 32 * DNW * DKM;   // 1280 keys (positions 0..1279)
@@ -91,7 +87,6 @@ struct DsImg {
 template <int G, int DS, int W0 = 0, int NWK = DNW, int VR = DKM>
 __device__ __forceinline__ void ds_tail(const AttnArgs& a, char* smem, uint4 (&vf)[VR][8 / DS], int qi, int kh,
                                         int s, int pos) {
-  constexpr int CPG = CH / 32;     // 32-key groups per chunk (the chunked kernel's waves)
   constexpr int DT = 8 / DS;       // 16-dim MFMA column tiles per slice
   using I = DsImg<G, DS>;
   constexpr int DSD = I::DSD;
@@ -103,7 +98,7 @@ __device__ __forceinline__ void ds_tail(const AttnArgs& a, char* smem, uint4 (&v
   float(&mblk)[DS_BLK][G] = *reinterpret_cast<float(*)[DS_BLK][G]>(smem + I::MB);
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int c16 = lane & 15, h4 = lane >> 4;
-  const int nk = pos + 1, n32 = (nk + 31) >> 5, nc = pos / CH + 1;
+  const int nk = pos + 1, n32 = groups_of(nk), nc = chunks_of(pos);
   ZMI_ASTAMP(3);
   // Softmax statistics. A wave takes the (chunk, head) tasks wave + DNW i; its tasks run interleaved
   // (independent LDS reads and DPP reductions), each with the chunked kernel's per-task arithmetic.
@@ -143,13 +138,7 @@ __device__ __forceinline__ void ds_tail(const AttnArgs& a, char* smem, uint4 (&v
         const int j = c / CPB, dep = min((j + 1) * CPB, nc);
         const float M = wave_max(lane < dep ? mjc[lane][g] : -INFINITY);  // exact: max is order-free
         if (c % CPB == 0 && lane == 0) mblk[j][g] = M;
-#pragma unroll
-        for (int ii = 0; ii < CH / 64; ++ii) {
-          const int key = c * CH + lane + 64 * ii;
-          const float e = key < nk ? expf(sc[g][key] - M) : 0.f;
-          l[i] += e;
-          pb[g][key] = (bf16_t)f2bf(e);
-        }
+        l[i] = exp_lane(&sc[g][c * CH], &pb[g][c * CH], M, nk - c * CH, lane);
       }
     }
 #pragma unroll
@@ -167,23 +156,11 @@ __device__ __forceinline__ void ds_tail(const AttnArgs& a, char* smem, uint4 (&v
   for (int r = 0; r < VR; ++r) {
     const int k = (wave - W0) + NWK * r;
     if (wave >= W0 && k < n32) {
-      uint4 pf = uint4{0u, 0u, 0u, 0u};
-      if (c16 < G) pf = *reinterpret_cast<const uint4*>(&pb[c16][32 * k + 8 * h4]);
       const int kbase = 32 * k + 8 * h4;
+      const uint4 pf = p_frag(pb, c16, kbase);
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt) {
-        uint4 v = vf[r][dt];
-        if (kbase + 8 > nk) {
-          uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const uint32_t lo = kbase + 2 * e < nk ? 0x0000ffffu : 0u;
-            const uint32_t hi = kbase + 2 * e + 1 < nk ? 0xffff0000u : 0u;
-            w[e] &= lo | hi;
-          }
-          v = uint4{w[0], w[1], w[2], w[3]};
-        }
-        const f32x4_t o = mfma16(pf, v, f32x4_t{0.f, 0.f, 0.f, 0.f});
+        const f32x4_t o = pv_tile(pf, v_keep(vf[r][dt], kbase, nk));
         if (h4 == 0) {
 #pragma unroll
           for (int i = 0; i < G; ++i) opart[k][i][16 * dt + c16] = o[i];
@@ -193,11 +170,12 @@ __device__ __forceinline__ void ds_tail(const AttnArgs& a, char* smem, uint4 (&v
   }
   __syncthreads();
   ZMI_ASTAMP(6);
-  // chunk sums and the block recursion (zmi_attn_merge.h), one thread per (head, dim of the slice);
+  // chunk sums and the block recursion (ChunkFold), one thread per (head, dim of the slice);
   // the chunk loop is unrolled to its bound so every LDS read issues ahead of the dependent adds
   if (t < G * DSD) {
     const int g = t / DSD, dl = t - g * DSD;
-    float acc = 0.f, l = 0.f, ob = 0.f, lb = 0.f, mprev = 0.f, mb = 0.f;
+    ChunkFold<> f;
+    float mb = 0.f;
 #pragma unroll
     for (int c = 0; c < DS_CH; ++c) {
       if (c < nc) {
@@ -205,29 +183,11 @@ __device__ __forceinline__ void ds_tail(const AttnArgs& a, char* smem, uint4 (&v
 #pragma unroll
         for (int w = 1; w < CPG; ++w)
           if (CPG * c + w < n32) oc += opart[CPG * c + w][g][dl];
-        if (c % CPB == 0) {
-          ob = oc;
-          lb = ljc[c][g];
-          mb = mblk[c / CPB][g];
-        } else {
-          ob += oc;
-          lb += ljc[c][g];
-        }
-        if (c % CPB == CPB - 1 || c == nc - 1) {
-          if (c < CPB) {
-            acc = ob;
-            l = lb;
-          } else {
-            const float et = expf(mprev - mb);
-            l = lb + et * l;
-            acc = acc * et + ob;
-          }
-          mprev = mb;
-        }
+        if (c % CPB == 0) mb = mblk[c / CPB][g];
+        f.add(c, nc, oc, ljc[c][g], mb);
       }
     }
-    const float rl = 1.0f / l;
-    a.out[(size_t)qi * a.ldo + (kh * G + g) * HD + DSD * s + dl] = (bf16_t)f2bf(acc * rl);
+    a.out[(size_t)qi * a.ldo + (kh * G + g) * HD + DSD * s + dl] = (bf16_t)f2bf(f.out());
   }
   ZMI_ASTAMP(7);
 }
@@ -236,7 +196,6 @@ __device__ __forceinline__ void ds_tail(const AttnArgs& a, char* smem, uint4 (&v
 // 8 apart (one XCD, speed only)
 template <int G, int DS>
 __device__ __forceinline__ void ds_body(const AttnArgs& a, int n_units, int b, char* smem) {
-  constexpr int CPG = CH / 32;     // 32-key groups per chunk (the chunked kernel's waves)
   constexpr int DT = 8 / DS;       // 16-dim MFMA column tiles per slice
   using I = DsImg<G, DS>;
   float(&sc)[G][DS_KEYS] = *reinterpret_cast<float(*)[G][DS_KEYS]>(smem + I::SC);
@@ -252,7 +211,7 @@ __device__ __forceinline__ void ds_body(const AttnArgs& a, int n_units, int b, c
   const int c16 = lane & 15, h4 = lane >> 4;
   const int kvr = a.kv_row ? a.kv_row[qi] : qi;
   const size_t kvbase = ((size_t)kvr * a.hkv + kh) * a.smax * HD;
-  const int nk = pos + 1, n32 = (nk + 31) >> 5, nc = pos / CH + 1;
+  const int nk = pos + 1, n32 = groups_of(nk), nc = chunks_of(pos);
 
   // every K and V^T fragment of this wave's groups k = wave + DNW r, in flight at once
   uint4 kf[DKM][2][4], vf[DKM][DT];
@@ -288,9 +247,7 @@ __device__ __forceinline__ void ds_body(const AttnArgs& a, int n_units, int b, c
     if (k < n32) {
 #pragma unroll
       for (int tt = 0; tt < 2; ++tt) {
-        f32x4_t sv = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int db = 0; db < 4; ++db) sv = mfma16(qf[db], kf[r][tt][db], sv);
+        const f32x4_t sv = score_tile(qf, kf[r][tt]);
         const int key = 32 * k + 16 * tt + c16;
         if (h4 == 0) {
 #pragma unroll

@@ -11,7 +11,7 @@
 // Arithmetic: the chunked kernel's, bit for bit, for every row (tests/test_gpu_attn_prefill.py compares with
 // zmi_attention_variant(variant = 1)). An MFMA output element does not depend on the other rows of its tile, and
 // every other step is stated per (row, key) or (row, dim) in zmi_attn_merge.h. For the row at position p:
-//   scores   the mfma16 chain over dim blocks 0..3 per 16-key sub-tile, * scale; keys > p are -inf by select;
+//   scores   score_tile (the mfma16 chain over dim blocks 0..3) per 16-key sub-tile, * scale; keys > p are -inf;
 //   M_j      max over the row's own keys of blocks 0..j;
 //   e, l, P  exp_chunk per 128-key chunk (lane L takes keys L and L + 64, wave_sum), P = bf16(e);
 //   P.V      per 32-key tile from a zero accumulator, a chunk's 4 tiles summed in tile order, the row's own
@@ -116,13 +116,13 @@ __global__ __launch_bounds__(PNT) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
 #pragma unroll
           for (int db = 0; db < 4; ++db) kf[k][tt][db] = *reinterpret_cast<const uint4*>(kb + ko + 32 * db);
         }
+      uint4 qf[4];
+#pragma unroll
+      for (int db = 0; db < 4; ++db) qf[db] = *reinterpret_cast<const uint4*>(&qs[c16][8 * h4 + 32 * db]);
 #pragma unroll
       for (int k = 0; k < 2; ++k)
 #pragma unroll
-        for (int db = 0; db < 4; ++db)
-#pragma unroll
-          for (int tt = 0; tt < 2; ++tt)
-            st[k][tt] = mfma16(*reinterpret_cast<const uint4*>(&qs[c16][8 * h4 + 32 * db]), kf[k][tt][db], st[k][tt]);
+        for (int tt = 0; tt < 2; ++tt) st[k][tt] = score_tile(qf, kf[k][tt]);
     }
 #pragma unroll
     for (int k = 0; k < 2; ++k)
@@ -176,10 +176,10 @@ __global__ __launch_bounds__(PNT) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const int kbase = 32 * (4 * cc + k) + 8 * h4;
-        const uint4 pf = *reinterpret_cast<const uint4*>(&pb[c16][kbase]);
+        const uint4 pf = p_frag(pb, c16, kbase);
 #pragma unroll
         for (int d4 = 0; d4 < 4; ++d4) {
-          const f32x4_t o = mfma16(pf, v_keep(vf[k][d4], kbase, nkeys), f32x4_t{0.f, 0.f, 0.f, 0.f});
+          const f32x4_t o = pv_tile(pf, v_keep(vf[k][d4], kbase, nkeys));
           os[d4] = k == 0 ? o : os[d4] + o;
         }
       }

@@ -19,9 +19,11 @@
 //   [0, n_qkv)           gemv_body (zmi_gemv_impl.h): LayerNorm prologue, the QKV projection for 16
 //                        columns, epilogue RoPE + KV-cache write + granules;
 //   [n_qkv, +units x S)  xs_body below.
-// The arithmetic is the separate kernels' operation for operation (bit-identical outputs, tested);
-// both roles run 512-thread workgroups: the projection with G = 2 groups x W = 4 waves, the K = 2048
-// shape every launch form uses.
+// The arithmetic is the separate kernels' operation for operation (bit-identical outputs, tested): every body
+// below calls zmi_attn_merge.h's statement of each step (score_tile, exp_lane / exp_chunk, v_keep, p_frag,
+// pv_tile, ChunkFold, and q_frag_lds / k_row_lds / patch_v_slot for this position's staged row); what a body
+// keeps for itself is its protocol, its load staging and the shape of its maxima. Both roles run 512-thread
+// workgroups: the projection with G = 2 groups x W = 4 waves, the K = 2048 shape every launch form uses.
 #include <algorithm>
 
 #include "zmi_common.h"
@@ -53,6 +55,51 @@ __device__ __forceinline__ void give_up(const AttnArgs& a) {
   __hip_atomic_store(a.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// One wave receives this position's q, K row and V row from the projection role: the unit's QKV_GRAN {bf16 pair,
+// tag} granules at gu, 6 per lane, polled with two sweeps in flight a fraction of a round trip apart (SLEEP between
+// them), then staged as pairs in LDS for the workgroup. Bounded: a give-up reports to err and stages what it has.
+template <int SLEEP>
+__device__ __forceinline__ void poll_qkv(const AttnArgs& a, const uint64_t* gu, uint32_t tag, uint32_t* qkv_lds,
+                                         int lane) {
+  uint64_t A[6], B[6];
+  auto sweep = [&](uint64_t(&g)[6]) {
+#pragma unroll
+    for (int i = 0; i < 6; ++i) g[i] = ld_wt64(gu + lane + 64 * i);
+  };
+  auto ready = [&](const uint64_t(&g)[6]) {
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) ok = ok && tag_of(g[i]) == tag;
+    return __all(ok);
+  };
+  auto stage = [&](const uint64_t(&g)[6]) {
+#pragma unroll
+    for (int i = 0; i < 6; ++i) qkv_lds[lane + 64 * i] = (uint32_t)g[i];
+  };
+  sweep(A);
+  __builtin_amdgcn_s_sleep(SLEEP);
+  sweep(B);
+  for (unsigned spins = 0;; spins += 2) {
+    if (ready(A)) {
+      stage(A);
+      break;
+    }
+    sweep(A);
+    __builtin_amdgcn_s_sleep(SLEEP);
+    if (ready(B)) {
+      stage(B);
+      break;
+    }
+    sweep(B);
+    __builtin_amdgcn_s_sleep(SLEEP);
+    if (spins > XS_SPIN) {
+      give_up(a);
+      stage(A);
+      break;
+    }
+  }
+}
+
 // Wave 0 of an attention workgroup only receives the projection's granules (it issues no K / V
 // loads, so its polls are not queued behind them); waves 1..7 ("workers") hold the K / V fragments.
 // Worker ww owns the 128-key chunks c = ww + XNWK rc: the V^T fragments of their four 32-key groups
@@ -60,7 +107,6 @@ __device__ __forceinline__ void give_up(const AttnArgs& a) {
 constexpr int XNWK = DNW - 1;                         // worker waves
 constexpr int XCH = DS_KEYS / CH;                     // chunks
 constexpr int XRC = (XCH + XNWK - 1) / XNWK;          // chunks per worker
-constexpr int CPG = CH / 32;                          // 32-key groups per chunk
 constexpr int XKPT = (DS_KEYS + NT - 1) / NT;         // keys per thread in the score gather
 
 template <int S>
@@ -107,7 +153,7 @@ __device__ __forceinline__ void xs_body(const AttnArgs& a, int n_units, int b, c
   const int c16 = lane & 15, h4 = lane >> 4;
   const int kvr = a.kv_row ? a.kv_row[qi] : qi;
   const size_t kvbase = ((size_t)kvr * a.hkv + kh) * a.smax * HD;
-  const int nk = pos + 1, n32 = (pos + 32) >> 5, nc = pos / CH + 1;
+  const int nk = pos + 1, n32 = groups_of(nk), nc = chunks_of(pos);
   uint64_t* gu = gran + (size_t)unit * GRAN_STRIDE;  // unit = query row x hkv + kv head, as the producers index
   uint64_t* gs = gu + QKV_GRAN;
 
@@ -142,81 +188,33 @@ __device__ __forceinline__ void xs_body(const AttnArgs& a, int n_units, int b, c
         }
       }
   } else {
-    // (2) wave 0: this position's q, K row and V row (QKV_GRAN pairs; 6 per lane), polled with two
-    // sweeps in flight a fraction of a round trip apart, then staged in LDS for the workers
-    uint64_t A[6], B[6];
-    auto sweep = [&](uint64_t(&g)[6]) {
-#pragma unroll
-      for (int i = 0; i < 6; ++i) g[i] = ld_wt64(gu + lane + 64 * i);
-    };
-    auto ready = [&](const uint64_t(&g)[6]) {
-      bool ok = true;
-#pragma unroll
-      for (int i = 0; i < 6; ++i) ok = ok && tag_of(g[i]) == tag;
-      return __all(ok);
-    };
-    auto stage = [&](const uint64_t(&g)[6]) {
-#pragma unroll
-      for (int i = 0; i < 6; ++i) qkv_lds[lane + 64 * i] = (uint32_t)g[i];
-    };
-    sweep(A);
-    __builtin_amdgcn_s_sleep(8);
-    sweep(B);
-    for (unsigned spins = 0;; spins += 2) {
-      if (ready(A)) {
-        stage(A);
-        break;
-      }
-      sweep(A);
-      __builtin_amdgcn_s_sleep(8);
-      if (ready(B)) {
-        stage(B);
-        break;
-      }
-      sweep(B);
-      __builtin_amdgcn_s_sleep(8);
-      if (spins > XS_SPIN) {
-        give_up(a);
-        stage(A);
-        break;
-      }
-    }
+    // (2) wave 0: this position's q, K row and V row, staged in LDS for the workers
+    poll_qkv<8>(a, gu, tag, qkv_lds, lane);
     ZMI_ASTAMP(1);
   }
   __syncthreads();
   uint4 qf[4];
   if (wave > 0) {
     const uint4* q4p = reinterpret_cast<const uint4*>(qkv_lds);
-#pragma unroll
-    for (int db = 0; db < 4; ++db)
-      qf[db] = c16 < XG ? q4p[(c16 * HD + 8 * h4 + 32 * db) >> 3] : uint4{0u, 0u, 0u, 0u};
+    q_frag_lds<XG>(qf, q4p, c16, h4);
     // the K row of pos replaces the fragment of the lane whose key it is; the V^T slot of pos is
     // patched in the fragment whose 8 positions hold it
 #pragma unroll
     for (int j = 0; j < KPW; ++j)
 #pragma unroll
       for (int tt = 0; tt < 2; ++tt)
-        if (ww + XNWK * j < OWN && 32 * (s + S * (ww + XNWK * j)) + 16 * tt + c16 == pos) {
-#pragma unroll
-          for (int db = 0; db < 4; ++db) kf[j][tt][db] = q4p[(XG * HD + 8 * h4 + 32 * db) >> 3];
-        }
+        if (ww + XNWK * j < OWN && 32 * (s + S * (ww + XNWK * j)) + 16 * tt + c16 == pos)
+          k_row_lds<XG>(kf[j][tt], q4p, h4);
 #pragma unroll
     for (int rc = 0; rc < XRC; ++rc)
 #pragma unroll
       for (int q4 = 0; q4 < CPG; ++q4) {
         const int kb = 32 * (CPG * (ww + XNWK * rc) + q4) + 8 * h4;
         if (kb <= pos && pos < kb + 8) {
-          const int sl = pos - kb, wi = sl >> 1, sh = (sl & 1) * 16;
 #pragma unroll
           for (int dt = 0; dt < DT; ++dt) {
             const int d = 16 * (DT * s + dt) + c16;
-            const uint32_t pr = qkv_lds[(XG + 1) * HD / 2 + (d >> 1)];
-            const uint32_t val = (d & 1) ? (pr >> 16) : (pr & 0xffffu);
-            uint32_t w[4] = {vf[rc][q4][dt].x, vf[rc][q4][dt].y, vf[rc][q4][dt].z, vf[rc][q4][dt].w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-              if (e == wi) w[e] = (w[e] & ~(0xffffu << sh)) | (val << sh);
-            vf[rc][q4][dt] = uint4{w[0], w[1], w[2], w[3]};
+            patch_v_slot(vf[rc][q4][dt], kb, pos, qkv_lds[(XG + 1) * HD / 2 + (d >> 1)], d);
           }
         }
       }
@@ -230,9 +228,7 @@ __device__ __forceinline__ void xs_body(const AttnArgs& a, int n_units, int b, c
     if (wave > 0 && ww + XNWK * j < OWN && k < n32) {
 #pragma unroll
       for (int tt = 0; tt < 2; ++tt) {
-        f32x4_t sv = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int db = 0; db < 4; ++db) sv = mfma16(qf[db], kf[j][tt][db], sv);
+        const f32x4_t sv = score_tile(qf, kf[j][tt]);
         const int key = 32 * k + 16 * tt + c16;
         if (h4 == 0 && key <= pos) {
 #pragma unroll
@@ -338,15 +334,7 @@ __device__ __forceinline__ void xs_body(const AttnArgs& a, int n_units, int b, c
         for (int cc = 1; cc < XCH; ++cc)  // unrolled: the LDS reads issue together
           if (cc < dep) M = fmaxf(M, mjc[cc][g]);
         if (c % CPB == 0 && lane == 0) mblk[j][g] = M;
-        float l = 0.f;
-#pragma unroll
-        for (int ii = 0; ii < CH / 64; ++ii) {
-          const int key = c * CH + lane + 64 * ii;
-          const float e = key < nk ? expf(sc[g][key] - M) : 0.f;
-          l += e;
-          pb[g][key] = (bf16_t)f2bf(e);
-        }
-        l = wave_sum(l);
+        const float l = exp_chunk(&sc[g][c * CH], &pb[g][c * CH], M, nk - c * CH, lane);
         if (lane == 0) ljc[c][g] = l;
       }
     }
@@ -367,23 +355,11 @@ __device__ __forceinline__ void xs_body(const AttnArgs& a, int n_units, int b, c
         for (int q4 = 0; q4 < CPG; ++q4) {
           const int k = CPG * c + q4;
           if (k < n32) {
-            uint4 pf = uint4{0u, 0u, 0u, 0u};
-            if (c16 < XG) pf = *reinterpret_cast<const uint4*>(&pb[c16][32 * k + 8 * h4]);
             const int kbase = 32 * k + 8 * h4;
+            const uint4 pf = p_frag(pb, c16, kbase);
 #pragma unroll
             for (int dt = 0; dt < DT; ++dt) {
-              uint4 v = vf[rc][q4][dt];
-              if (kbase + 8 > nk) {
-                uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                  const uint32_t lo = kbase + 2 * e < nk ? 0x0000ffffu : 0u;
-                  const uint32_t hi = kbase + 2 * e + 1 < nk ? 0xffff0000u : 0u;
-                  w[e] &= lo | hi;
-                }
-                v = uint4{w[0], w[1], w[2], w[3]};
-              }
-              const f32x4_t o = mfma16(pf, v, f32x4_t{0.f, 0.f, 0.f, 0.f});
+              const f32x4_t o = pv_tile(pf, v_keep(vf[rc][q4][dt], kbase, nk));
               if (q4 == 0) {
                 oc[dt] = o;
               } else {
@@ -406,10 +382,11 @@ __device__ __forceinline__ void xs_body(const AttnArgs& a, int n_units, int b, c
   }
   __syncthreads();
   ZMI_ASTAMP(5);
-  // (7) the block recursion (zmi_attn_merge.h), one thread per (head, dim of the slice)
+  // (7) the block recursion (ChunkFold), one thread per (head, dim of the slice)
   if (t < XG * DSD) {
     const int g = t / DSD, dl = t - g * DSD;
-    float acc = 0.f, l = 0.f, ob = 0.f, lb = 0.f, mprev = 0.f, mb = 0.f;
+    ChunkFold<> f;
+    float mb = 0.f;
     float ocv[XCH], lcv[XCH];
 #pragma unroll
     for (int c = 0; c < XCH; ++c) {  // every read first (clamped rows past nc are never used)
@@ -420,29 +397,10 @@ __device__ __forceinline__ void xs_body(const AttnArgs& a, int n_units, int b, c
 #pragma unroll
     for (int c = 0; c < XCH; ++c) {
       if (c >= nc) break;
-      const float oc = ocv[c];
-      if (c % CPB == 0) {
-        ob = oc;
-        lb = lcv[c];
-        mb = mblk[c / CPB][g];
-      } else {
-        ob += oc;
-        lb += lcv[c];
-      }
-      if (c % CPB == CPB - 1 || c == nc - 1) {
-        if (c < CPB) {
-          acc = ob;
-          l = lb;
-        } else {
-          const float et = expf(mprev - mb);
-          l = lb + et * l;
-          acc = acc * et + ob;
-        }
-        mprev = mb;
-      }
+      if (c % CPB == 0) mb = mblk[c / CPB][g];
+      f.add(c, nc, ocv[c], lcv[c], mb);
     }
-    const float rl = 1.0f / l;
-    a.out[(size_t)qi * a.ldo + (kh * XG + g) * HD + DSD * s + dl] = (bf16_t)f2bf(acc * rl);
+    a.out[(size_t)qi * a.ldo + (kh * XG + g) * HD + DSD * s + dl] = (bf16_t)f2bf(f.out());
   }
   ZMI_ASTAMP(6);
 }
@@ -503,7 +461,7 @@ __device__ __forceinline__ void xr_body(const AttnArgs& a, int n_units, int b, c
   const int c16 = lane & 15, h4 = lane >> 4;
   const int kvr = a.kv_row ? a.kv_row[qi] : qi;
   const size_t kvbase = ((size_t)kvr * a.hkv + kh) * a.smax * HD;
-  const int nk = pos + 1, n32 = (pos + 32) >> 5, nc = pos / CH + 1;
+  const int nk = pos + 1, n32 = groups_of(nk), nc = chunks_of(pos);
   const int c = wave;                      // this wave's chunk
   const bool live = c < nc;
   uint64_t* gu = gran + (size_t)unit * GRAN_STRIDE;
@@ -537,44 +495,8 @@ __device__ __forceinline__ void xr_body(const AttnArgs& a, int n_units, int b, c
     }
   }
   if (wave == XR_POLL) {
-    // (2) this position's q, K row and V row (QKV_GRAN pairs; 6 per lane), two sweeps in flight
-    uint64_t A[6], B[6];
-    auto sweep = [&](uint64_t(&g)[6]) {
-#pragma unroll
-      for (int i = 0; i < 6; ++i) g[i] = ld_wt64(gu + lane + 64 * i);
-    };
-    auto ready = [&](const uint64_t(&g)[6]) {
-      bool ok = true;
-#pragma unroll
-      for (int i = 0; i < 6; ++i) ok = ok && tag_of(g[i]) == tag;
-      return __all(ok);
-    };
-    auto stage = [&](const uint64_t(&g)[6]) {
-#pragma unroll
-      for (int i = 0; i < 6; ++i) qkv_lds[lane + 64 * i] = (uint32_t)g[i];
-    };
-    sweep(A);
-    __builtin_amdgcn_s_sleep(8);
-    sweep(B);
-    for (unsigned spins = 0;; spins += 2) {
-      if (ready(A)) {
-        stage(A);
-        break;
-      }
-      sweep(A);
-      __builtin_amdgcn_s_sleep(8);
-      if (ready(B)) {
-        stage(B);
-        break;
-      }
-      sweep(B);
-      __builtin_amdgcn_s_sleep(8);
-      if (spins > XS_SPIN) {
-        give_up(a);
-        stage(A);
-        break;
-      }
-    }
+    // (2) this position's q, K row and V row
+    poll_qkv<8>(a, gu, tag, qkv_lds, lane);
     ZMI_ASTAMP(1);
   }
   __syncthreads();
@@ -584,32 +506,20 @@ __device__ __forceinline__ void xr_body(const AttnArgs& a, int n_units, int b, c
   if (live) {
     const uint4* q4p = reinterpret_cast<const uint4*>(qkv_lds);
     uint4 qf[4];
-#pragma unroll
-    for (int db = 0; db < 4; ++db)
-      qf[db] = c16 < XG ? q4p[(c16 * HD + 8 * h4 + 32 * db) >> 3] : uint4{0u, 0u, 0u, 0u};
+    q_frag_lds<XG>(qf, q4p, c16, h4);
 #pragma unroll
     for (int q4 = 0; q4 < CPG; ++q4)
 #pragma unroll
       for (int tt = 0; tt < 2; ++tt)
-        if (32 * (CPG * c + q4) + 16 * tt + c16 == pos) {
-#pragma unroll
-          for (int db = 0; db < 4; ++db) kf[q4][tt][db] = q4p[(XG * HD + 8 * h4 + 32 * db) >> 3];
-        }
+        if (32 * (CPG * c + q4) + 16 * tt + c16 == pos) k_row_lds<XG>(kf[q4][tt], q4p, h4);
 #pragma unroll
     for (int q4 = 0; q4 < CPG; ++q4) {
       const int kb = 32 * (CPG * c + q4) + 8 * h4;
       if (kb <= pos && pos < kb + 8) {
-        const int sl = pos - kb, wi = sl >> 1, sh = (sl & 1) * 16;
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt) {
           const int d = 16 * (DT * s + dt) + c16;
-          const uint32_t pr = qkv_lds[(XG + 1) * HD / 2 + (d >> 1)];
-          const uint32_t val = (d & 1) ? (pr >> 16) : (pr & 0xffffu);
-          uint32_t w[4] = {vf[q4][dt].x, vf[q4][dt].y, vf[q4][dt].z, vf[q4][dt].w};
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (e == wi) w[e] = (w[e] & ~(0xffffu << sh)) | (val << sh);
-          vf[q4][dt] = uint4{w[0], w[1], w[2], w[3]};
+          patch_v_slot(vf[q4][dt], kb, pos, qkv_lds[(XG + 1) * HD / 2 + (d >> 1)], d);
         }
       }
     }
@@ -619,9 +529,7 @@ __device__ __forceinline__ void xr_body(const AttnArgs& a, int n_units, int b, c
       if (k < n32) {
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt) {
-          f32x4_t sv = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-          for (int db = 0; db < 4; ++db) sv = mfma16(qf[db], kf[q4][tt][db], sv);
+          const f32x4_t sv = score_tile(qf, kf[q4][tt]);
           const int key = 32 * k + 16 * tt + c16;
           if (h4 == 0 && key <= pos) {
 #pragma unroll
@@ -660,14 +568,7 @@ __device__ __forceinline__ void xr_body(const AttnArgs& a, int n_units, int b, c
       for (int cc = 1; cc < XR_CH; ++cc)
         if (cc < dep) M = fmaxf(M, mjc[cc][g]);
       if (c % CPB == 0 && lane == 0) mblk[j][g] = M;
-      l[g] = 0.f;
-#pragma unroll
-      for (int ii = 0; ii < CH / 64; ++ii) {
-        const int key = c * CH + lane + 64 * ii;
-        const float e = key < nk ? expf(sc[g][key] - M) : 0.f;
-        l[g] += e;
-        pb[g][key] = (bf16_t)f2bf(e);
-      }
+      l[g] = exp_lane(&sc[g][c * CH], &pb[g][c * CH], M, nk - c * CH, lane);
     }
 #pragma unroll
     for (int g = 0; g < XG; ++g) l[g] = wave_sum(l[g]);
@@ -682,23 +583,11 @@ __device__ __forceinline__ void xr_body(const AttnArgs& a, int n_units, int b, c
     for (int q4 = 0; q4 < CPG; ++q4) {
       const int k = CPG * c + q4;
       if (k < n32) {
-        uint4 pf = uint4{0u, 0u, 0u, 0u};
-        if (c16 < XG) pf = *reinterpret_cast<const uint4*>(&pb[c16][32 * k + 8 * h4]);
         const int kbase = 32 * k + 8 * h4;
+        const uint4 pf = p_frag(pb, c16, kbase);
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt) {
-          uint4 v = vf[q4][dt];
-          if (kbase + 8 > nk) {
-            uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              const uint32_t lo = kbase + 2 * e < nk ? 0x0000ffffu : 0u;
-              const uint32_t hi = kbase + 2 * e + 1 < nk ? 0xffff0000u : 0u;
-              w[e] &= lo | hi;
-            }
-            v = uint4{w[0], w[1], w[2], w[3]};
-          }
-          const f32x4_t o = mfma16(pf, v, f32x4_t{0.f, 0.f, 0.f, 0.f});
+          const f32x4_t o = pv_tile(pf, v_keep(vf[q4][dt], kbase, nk));
           if (q4 == 0) {
             oc[dt] = o;
           } else {
@@ -719,10 +608,11 @@ __device__ __forceinline__ void xr_body(const AttnArgs& a, int n_units, int b, c
   }
   __syncthreads();
   ZMI_ASTAMP(5);
-  // (5) the block recursion (zmi_attn_merge.h), one thread per (head, dim of the slice)
+  // (5) the block recursion (ChunkFold), one thread per (head, dim of the slice)
   if (t < XG * DSD) {
     const int g = t / DSD, dl = t - g * DSD;
-    float acc = 0.f, l = 0.f, ob = 0.f, lb = 0.f, mprev = 0.f, mb = 0.f;
+    ChunkFold<> f;
+    float mb = 0.f;
     float ocv[XR_CH], lcv[XR_CH];
 #pragma unroll
     for (int cc = 0; cc < XR_CH; ++cc) {
@@ -733,29 +623,10 @@ __device__ __forceinline__ void xr_body(const AttnArgs& a, int n_units, int b, c
 #pragma unroll
     for (int cc = 0; cc < XR_CH; ++cc) {
       if (cc >= nc) break;
-      const float o = ocv[cc];
-      if (cc % CPB == 0) {
-        ob = o;
-        lb = lcv[cc];
-        mb = mblk[cc / CPB][g];
-      } else {
-        ob += o;
-        lb += lcv[cc];
-      }
-      if (cc % CPB == CPB - 1 || cc == nc - 1) {
-        if (cc < CPB) {
-          acc = ob;
-          l = lb;
-        } else {
-          const float et = expf(mprev - mb);
-          l = lb + et * l;
-          acc = acc * et + ob;
-        }
-        mprev = mb;
-      }
+      if (cc % CPB == 0) mb = mblk[cc / CPB][g];
+      f.add(cc, nc, ocv[cc], lcv[cc], mb);
     }
-    const float rl = 1.0f / l;
-    a.out[(size_t)qi * a.ldo + (kh * XG + g) * HD + DSD * s + dl] = (bf16_t)f2bf(acc * rl);
+    a.out[(size_t)qi * a.ldo + (kh * XG + g) * HD + DSD * s + dl] = (bf16_t)f2bf(f.out());
   }
   ZMI_ASTAMP(6);
 }
@@ -824,7 +695,7 @@ __device__ __forceinline__ void xc_body(const AttnArgs& a, int n_units, int b, c
   const uint64_t tag64 = (uint64_t)tag << 32;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int c16 = lane & 15, h4 = lane >> 4;
-  const int nk = pos + 1, n32 = (pos + 32) >> 5, nc = pos / CH + 1;
+  const int nk = pos + 1, n32 = groups_of(nk), nc = chunks_of(pos);
   uint64_t* gu = gran + (size_t)unit * GRAN_STRIDE;
   uint64_t* gx = gu + QKV_GRAN;
 
@@ -849,44 +720,8 @@ __device__ __forceinline__ void xc_body(const AttnArgs& a, int n_units, int b, c
         vf[dt] = *reinterpret_cast<const uint4*>(a.v + kvbase + (size_t)(64 * hv + 16 * dt + c16) * a.smax + p0);
     }
     if (wave == 0) {
-      // (2) this position's q, K row and V row (QKV_GRAN pairs; 6 per lane), two sweeps in flight
-      uint64_t A[6], B[6];
-      auto sweep = [&](uint64_t(&g)[6]) {
-#pragma unroll
-        for (int i = 0; i < 6; ++i) g[i] = ld_wt64(gu + lane + 64 * i);
-      };
-      auto ready = [&](const uint64_t(&g)[6]) {
-        bool ok = true;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) ok = ok && tag_of(g[i]) == tag;
-        return __all(ok);
-      };
-      auto stage = [&](const uint64_t(&g)[6]) {
-#pragma unroll
-        for (int i = 0; i < 6; ++i) qkv_lds[lane + 64 * i] = (uint32_t)g[i];
-      };
-      sweep(A);
-      __builtin_amdgcn_s_sleep(ZMI_XC_QKV_SLEEP);
-      sweep(B);
-      for (unsigned spins = 0;; spins += 2) {
-        if (ready(A)) {
-          stage(A);
-          break;
-        }
-        sweep(A);
-        __builtin_amdgcn_s_sleep(ZMI_XC_QKV_SLEEP);
-        if (ready(B)) {
-          stage(B);
-          break;
-        }
-        sweep(B);
-        __builtin_amdgcn_s_sleep(ZMI_XC_QKV_SLEEP);
-        if (spins > XS_SPIN) {
-          give_up(a);
-          stage(A);
-          break;
-        }
-      }
+      // (2) this position's q, K row and V row
+      poll_qkv<ZMI_XC_QKV_SLEEP>(a, gu, tag, qkv_lds, lane);
       ZMI_ASTAMP(1);
     }
     __syncthreads();
@@ -894,17 +729,10 @@ __device__ __forceinline__ void xc_body(const AttnArgs& a, int n_units, int b, c
     const uint4* q4p = reinterpret_cast<const uint4*>(qkv_lds);
     if (sk) {
       uint4 qf[4];
-#pragma unroll
-      for (int db = 0; db < 4; ++db)
-        qf[db] = c16 < XG ? q4p[(c16 * HD + 8 * h4 + 32 * db) >> 3] : uint4{0u, 0u, 0u, 0u};
+      q_frag_lds<XG>(qf, q4p, c16, h4);
       const int key = CH * c + 32 * gs + 16 * tt + c16;
-      if (key == pos) {
-#pragma unroll
-        for (int db = 0; db < 4; ++db) kf[db] = q4p[(XG * HD + 8 * h4 + 32 * db) >> 3];
-      }
-      f32x4_t sv = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int db = 0; db < 4; ++db) sv = mfma16(qf[db], kf[db], sv);
+      if (key == pos) k_row_lds<XG>(kf, q4p, h4);
+      const f32x4_t sv = score_tile(qf, kf);
       if (h4 == 0 && key <= pos) {
 #pragma unroll
         for (int i = 0; i < XG; ++i) sc[i][key - CH * c] = sv[i] * a.scale;
@@ -913,17 +741,10 @@ __device__ __forceinline__ void xc_body(const AttnArgs& a, int n_units, int b, c
     if (vk) {  // the V^T slot of pos, in the fragment whose 8 positions hold it
       const int kb = CH * c + 32 * gv + 8 * h4;
       if (kb <= pos && pos < kb + 8) {
-        const int sl = pos - kb, wi = sl >> 1, sh = (sl & 1) * 16;
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
           const int d = 64 * hv + 16 * dt + c16;
-          const uint32_t pr = qkv_lds[(XG + 1) * HD / 2 + (d >> 1)];
-          const uint32_t val = (d & 1) ? (pr >> 16) : (pr & 0xffffu);
-          uint32_t w[4] = {vf[dt].x, vf[dt].y, vf[dt].z, vf[dt].w};
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (e == wi) w[e] = (w[e] & ~(0xffffu << sh)) | (val << sh);
-          vf[dt] = uint4{w[0], w[1], w[2], w[3]};
+          patch_v_slot(vf[dt], kb, pos, qkv_lds[(XG + 1) * HD / 2 + (d >> 1)], d);
         }
       }
     }
@@ -976,15 +797,7 @@ __device__ __forceinline__ void xc_body(const AttnArgs& a, int n_units, int b, c
     // (5) waves 0..3 (head w): e = exp(s - M_j), l (lane L: keys L, L + 64, then wave_sum), P = bf16(e)
     if (wave < XG) {
       const float M = mj[wave];
-      float l = 0.f;
-#pragma unroll
-      for (int ii = 0; ii < CH / 64; ++ii) {
-        const int kk = lane + 64 * ii;
-        const float e = CH * c + kk < nk ? expf(sc[wave][kk] - M) : 0.f;
-        l += e;
-        pb[wave][kk] = (bf16_t)f2bf(e);
-      }
-      l = wave_sum(l);
+      const float l = exp_chunk(sc[wave], pb[wave], M, nk - CH * c, lane);
       if (lane == 0) {
         st_xc64(gx + XC_GL + c * XG + wave, (uint64_t)__float_as_uint(l) | tag64, a.xc_l2);
         st_xc64(gx + XC_GB + c * XG + wave, (uint64_t)__float_as_uint(M) | tag64, a.xc_l2);
@@ -994,23 +807,11 @@ __device__ __forceinline__ void xc_body(const AttnArgs& a, int n_units, int b, c
     ZMI_ASTAMP(4);
     // (6) P.V of group w & 3 for dims 64 (w >> 2) .. + 63 (V of keys past the position zeroed)
     if (vk) {
-      uint4 pf = uint4{0u, 0u, 0u, 0u};
-      if (c16 < XG) pf = *reinterpret_cast<const uint4*>(&pb[c16][32 * gv + 8 * h4]);
+      const uint4 pf = p_frag(pb, c16, 32 * gv + 8 * h4);
       const int kbase = CH * c + 32 * gv + 8 * h4;
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
-        uint4 v = vf[dt];
-        if (kbase + 8 > nk) {
-          uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const uint32_t lo = kbase + 2 * e < nk ? 0x0000ffffu : 0u;
-            const uint32_t hi = kbase + 2 * e + 1 < nk ? 0xffff0000u : 0u;
-            w[e] &= lo | hi;
-          }
-          v = uint4{w[0], w[1], w[2], w[3]};
-        }
-        const f32x4_t o = mfma16(pf, v, f32x4_t{0.f, 0.f, 0.f, 0.f});
+        const f32x4_t o = pv_tile(pf, v_keep(vf[dt], kbase, nk));
         if (h4 == 0) {
 #pragma unroll
           for (int i = 0; i < XG; ++i) opart[gv][i][64 * hv + 16 * dt + c16] = o[i];
@@ -1086,31 +887,13 @@ __device__ __forceinline__ void xc_body(const AttnArgs& a, int n_units, int b, c
     const float* mO = reinterpret_cast<const float*>(smem + XcImg::OP);
     const float* mL = reinterpret_cast<const float*>(smem + XcImg::SC);
     const float* mM = mL + XC_CH * XG;
-    float acc = 0.f, l = 0.f, ob = 0.f, lb = 0.f, mprev = 0.f, mb = 0.f;
+    ChunkFold<> f;
+    float mb = 0.f;
     for (int k = 0; k < nc; ++k) {
-      const float o = mO[k * (XG * 16) + t], lk = mL[k * XG + g];
-      if (k % CPB == 0) {
-        ob = o;
-        lb = lk;
-        mb = mM[(k / CPB) * XG + g];
-      } else {
-        ob += o;
-        lb += lk;
-      }
-      if (k % CPB == CPB - 1 || k == nc - 1) {
-        if (k < CPB) {
-          acc = ob;
-          l = lb;
-        } else {
-          const float et = expf(mprev - mb);
-          l = lb + et * l;
-          acc = acc * et + ob;
-        }
-        mprev = mb;
-      }
+      if (k % CPB == 0) mb = mM[(k / CPB) * XG + g];
+      f.add(k, nc, mO[k * (XG * 16) + t], mL[k * XG + g], mb);
     }
-    const float rl = 1.0f / l;
-    const uint32_t ov16 = f2bf(acc * rl);
+    const uint32_t ov16 = f2bf(f.out());
     a.out[(size_t)qi * a.ldo + (kh * XG + g) * HD + d] = (bf16_t)ov16;
     if constexpr (OPROJ) {
       // the same 64 values as 32 {bf16 pair, tag} granules for the out_proj role (this is wave 0: its lanes t hold
